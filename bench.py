@@ -12,17 +12,25 @@ the default) or count + order-independent checksum of the (start, end, value) st
   --scaling strong  ONE haystack of --bytes (default 4 GiB) split over the ranks with daac_scan_count_range: rank r
                     generates bytes [lo_r - halo, hi_r) of the stream and counts the matches ending in (lo_r, hi_r]
 
-`python bench.py --gpus N` launches itself: without WORLD_SIZE in the environment it re-executes under
-`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU
+`python bench.py --gpus N` launches itself: without WORLD_SIZE in the environment it runs
+`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` as a child process, one rank per GPU
 (N must not exceed hipGetDeviceCount).  Under a launcher (WORLD_SIZE set) it is one rank of the job.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; beside the
+headline it carries only what those timed steps measured:
   roofline      dominant kernel vs the HBM roof: algorithmic bytes (= haystack bytes, 1 B read per haystack byte) /
-                average kernel time measured with HIP events on the launch stream
-  dense         the same automaton and kernel over the word-soup haystack (cfg3 (ii)), N = 1 only
+                average kernel time measured with HIP events on the launch stream (traffic and method ceiling: committed
+                figures from separate profiling runs, read from profiles/)
+--dump-outputs DIR writes what the last timed step returned (the match count; with --op checksum also the checksum) as
+DIR/*.npy, float64, so that two builds can be compared output for output on the same seeded inputs.
+--full adds every other leg, N = 1 only unless stated (--no-cpu, --no-dense, --no-extra, --materialize-mib trim it):
+  with_checksum / count_only  the other op on the same haystack; the two kernels must agree on the count
+  dense         the same automaton and kernel over the word-soup haystack (cfg3 (ii))
   cpu_baseline  the C restatement of the reference's CPU path (oracle/, kind "port"), built -O3 -march=native on
                 this host, timed on a bounded prefix of the same haystack with a 1/2/4/... thread ladder; count +
                 checksum checked against the GPU's for that prefix
+  tuples_device[_24], materialize, wide_alphabet, any_alphabet, restart, cfg5, iterator, stream, multi
+  distributed.strong_equals_one_rank  (N > 1, --scaling strong) the job's result against one device's scan of the whole
 """
 import argparse
 import json
@@ -59,6 +67,11 @@ def parse_args(argv=None):
     ap.add_argument("--plumbing", action="store_true",
                     help="no GPU, no scan: every rank contributes a fixed triple; exercises launch, rendezvous, reduction and the "
                          "JSON line only (used by the CPU test of the N > 1 path; prints value null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (other op, dense, CPU baseline, tuples, other dictionaries, iterators, "
+                         "strong-scaling self-check); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -122,6 +135,17 @@ def traffic_stale():
         return None
 
 
+def dump_outputs(dirname, count, checksum):
+    """What a caller of the timed path receives from the last timed step (after the reduce over ranks): match_count.npy = [count]
+    and, with --op checksum, match_checksum.npy = [high 32 bits, low 32 bits] of the 64-bit checksum.  float64 holds every value
+    exactly (count < 2^53, halves < 2^32)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "match_count.npy"), np.array([count], dtype=np.float64))
+    if checksum is not None:
+        np.save(os.path.join(dirname, "match_checksum.npy"), np.array([checksum >> 32, checksum & 0xFFFFFFFF], dtype=np.float64))
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -129,7 +153,9 @@ def free_port():
 
 
 def self_launch(args):
-    """--gpus N without a launcher: check N against the device count and re-exec under torchrun."""
+    """--gpus N without a launcher: check N against the device count and run torchrun as a child process (this process has
+    initialised the HIP runtime, so it is not replaced); exits with the child's status."""
+    import subprocess
     if not args.plumbing:
         import torch
         have = torch.cuda.device_count()  # hipGetDeviceCount
@@ -139,7 +165,7 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def cpu_limits():
@@ -640,7 +666,7 @@ def main():
             "rccl_version": (".".join(str(x) for x in torch.cuda.nccl.version()) if backend == "nccl" and hasattr(torch.cuda, "nccl") else None),
         })
         # strong scaling: the job's count (+ checksum) must be what ONE device finds in the whole haystack — checked here, not only in the tests
-        if args.scaling == "strong" and world > 1 and total <= (8 << 30):
+        if args.full and args.scaling == "strong" and world > 1 and total <= (8 << 30):
             ok = None
             if rank == 0:
                 whole = torch.empty(total, dtype=torch.uint8, device="cuda")
@@ -660,6 +686,8 @@ def main():
         dist = None
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, total_count, checksum)
 
     value = job_bytes * args.steps / elapsed / 1e9
     achieved = nbytes / avg_kernel_s / 1e9
@@ -706,8 +734,10 @@ def main():
     out["roofline"]["traffic"], out["roofline"]["traffic_source"] = tr
     out["roofline"]["traffic_stale"] = traffic_stale()
 
+    full = args.full and world == 1   # every leg below is --full, on one rank
+
     # ---- tuples (reported, not the metric): device-resident list of a 1 GiB prefix in both device formats, and a list copied to the host ----
-    if args.materialize_mib > 0 and world == 1:
+    if full and args.materialize_mib > 0:
         da.set_option("max_result_bytes", 64 << 30)
         n = min(nbytes, 1 << 30)
         for key, fmt16, tb in (("tuples_device", True, 16), ("tuples_device_24", False, 24)):
@@ -743,7 +773,7 @@ def main():
         del m
 
     # ---- CPU baseline: the C restatement of the reference CPU path, on a bounded prefix ----------------
-    if not args.no_cpu and world == 1:
+    if full and not args.no_cpu:
         os.environ["DAAC_ORACLE_NATIVE"] = "1"  # -O3 -march=native, built on this host
         from oracle import oracle as orc
         o = orc.OraclePma.deserialize(pma.serialize())
@@ -805,7 +835,7 @@ def main():
         del sample
 
     # ---- the other op beside the primary one: same haystack, few steps; the two kernels must agree on the count -----------
-    if world == 1:
+    if full:
         other = "checksum" if args.op == "count" else "count"
         op["v"] = other
         _, k_s = timed(max(3, args.steps // 4), 1)
@@ -822,7 +852,7 @@ def main():
         op["v"] = args.op
 
     # ---- the dense haystack (cfg3 (ii): word soup) beside the primary number --------------------------
-    if world == 1 and not args.no_dense and args.haystack == "sparse":
+    if full and not args.no_dense and args.haystack == "sparse":
         fill("dense")
         _, k_s = timed(max(3, args.steps // 4), 1)
         cnt = int(result[0].item())
@@ -845,7 +875,7 @@ def main():
                         "parity_whole_haystack": dense_parity,
                         "traffic": hbm_traffic("cfg3_dense_count", "gram4_kernel")[0] if args.workload == "cfg3" and args.op == "count" else None}
     # ---- a dictionary beyond 31 byte classes: the cfg3 words in mixed case + digits (60 pattern bytes) -----------------
-    if world == 1 and not args.no_dense and args.workload == "cfg3":
+    if full and not args.no_dense and args.workload == "cfg3":
         del hay
         torch.cuda.empty_cache()
         wp = da.DoubleArrayAhoCorasick.new(synth.patterns_cfg3_wide())
@@ -958,7 +988,7 @@ def main():
             torch.cuda.empty_cache()
         out["any_alphabet"] = anyab
     # ---- the other iterators of the path and configs[4], under this same clock; the lazy iterator over host haystacks ----
-    if world == 1 and not args.no_extra and args.workload == "cfg3" and args.haystack == "sparse":
+    if full and not args.no_extra and args.workload == "cfg3" and args.haystack == "sparse":
         try:
             hay_alive = hay  # noqa: F841
             del hay

@@ -114,7 +114,7 @@ def test_bench_two_ranks_on_one_gpu_weak_and_strong():
     common = ["--steps", "2", "--warmup", "1", "--no-cpu", "--no-dense", "--materialize-mib", "0", "--workload", "cfg2", "--op", "checksum"]
     env = {"DAAC_DIST_BACKEND": "gloo", "DAAC_BENCH_OVERSUBSCRIBE": "1"}
     one = _run_bench(["--gpus", "1", "--bytes", str(96 << 20)] + common)
-    strong = _run_bench(["--gpus", "2", "--scaling", "strong", "--bytes", str(96 << 20)] + common, env)
+    strong = _run_bench(["--gpus", "2", "--scaling", "strong", "--bytes", str(96 << 20), "--full"] + common, env)
     assert strong["n_gpus"] == 2 and strong["scaling"] == "strong"
     assert strong["match_count"] == one["match_count"] and strong["match_checksum"] == one["match_checksum"]
     assert strong["config"]["haystack_bytes_job"] == 96 << 20 and strong["config"]["engine_used"] == "gram"
@@ -127,6 +127,19 @@ def test_bench_two_ranks_on_one_gpu_weak_and_strong():
     # the default op (.count() alone) under strong scaling: same count, no checksum in the line
     cnt = _run_bench(["--gpus", "2", "--scaling", "strong", "--bytes", str(96 << 20)] + common[:-2], env)
     assert cnt["match_count"] == one["match_count"] and cnt["match_checksum"] is None and cnt["op"].endswith(".count()")
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_timed_step_returned(tmp_path):
+    """--dump-outputs: the last timed step's count and checksum as float64 .npy, equal to the line's own; a plain run carries none of
+    the --full legs."""
+    line = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg2", "--bytes", str(64 << 20), "--op", "checksum",
+                       "--dump-outputs", str(tmp_path)])
+    cnt, cs = np.load(tmp_path / "match_count.npy"), np.load(tmp_path / "match_checksum.npy")
+    assert cnt.dtype == np.float64 and cs.dtype == np.float64 and cnt.shape == (1,) and cs.shape == (2,)
+    assert int(cnt[0]) == line["match_count"] > 0 and f"{(int(cs[0]) << 32) | int(cs[1]):016x}" == line["match_checksum"]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert not {"count_only", "with_checksum", "dense", "cpu_baseline", "materialize"} & set(line)
 
 
 @pytest.mark.gpu

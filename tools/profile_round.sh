@@ -40,7 +40,7 @@ PY
   echo "== $name"; head -5 $OUT/${TAG}_${name}_kernel_stats.csv; cat $P/${name}_hbm.json | head -14
 }
 
-B="python $R/bench.py --steps 8 --warmup 2 --no-cpu --no-dense --materialize-mib 0 --no-extra"
+B="python $R/bench.py --full --steps 8 --warmup 2 --no-cpu --no-dense --materialize-mib 0 --no-extra"
 profile cfg3_sparse_count    "gram4_kernel,gram2_kernel,gram_count_kernel" 2 $B
 profile cfg3_sparse_checksum "gram_count_kernel,gram2_kernel" 2 $B --op checksum
 profile cfg3_dense_count     "gram4_kernel" 2 $B --haystack dense
@@ -120,10 +120,10 @@ cd /tmp
 
 # the bench lines themselves (they read the traffic file given here; in the repository: profiles/hbm_traffic.json)
 export DAAC_HBM_TRAFFIC_JSON=$OUT/${TAG}_hbm_traffic.json
-python $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python $R/bench.py --op checksum --no-cpu --no-dense --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg3_checksum.json 2>> $OUT/${TAG}_bench.err
-python $R/bench.py --haystack dense --no-cpu --no-dense --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg3_dense.json 2>> $OUT/${TAG}_bench.err
-python $R/bench.py --workload cfg2 --bytes 1073741824 --no-cpu --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg2.json 2>> $OUT/${TAG}_bench.err
+python $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python $R/bench.py --full --op checksum --no-cpu --no-dense --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg3_checksum.json 2>> $OUT/${TAG}_bench.err
+python $R/bench.py --full --haystack dense --no-cpu --no-dense --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg3_dense.json 2>> $OUT/${TAG}_bench.err
+python $R/bench.py --full --workload cfg2 --bytes 1073741824 --no-cpu --materialize-mib 0 --no-extra > $OUT/${TAG}_bench_cfg2.json 2>> $OUT/${TAG}_bench.err
 python $R/tools/time_find.py 1024 sparse > $OUT/${TAG}_find_sparse.txt 2>&1
 python $R/tools/time_find.py 1024 dense > $OUT/${TAG}_find_dense.txt 2>&1
 python $R/tools/time_find_tuples.py 1024 sparse > $OUT/${TAG}_find_tuples.txt 2>&1
