@@ -22,11 +22,16 @@
 // dictionary words (their own probe) keep that directory and the TAIL body.  1 400 -> 1 500 GB/s on cfg3 (profiles/r06_gram4_decomposition.txt).
 // (b) the hit queues hold 16-bit offsets into the wave's text slot (4 KB more for the Bloom array).  (c) walker positions are offsets
 // from a 2 GiB epoch base: they no longer wrap when a walker crosses a multiple of 4 GiB.
+// Round 7: the hit queue by a wave prefix sum — each lane's hits go to [its first index, + popc(H)) of a linear 256-entry list per wave, 5 VALU
+// a turn instead of 9 (ballot, two mbcnt and a ring address every turn), batches of 64 cut once the step's hits are in; a step with more
+// hits than the list holds runs the scan again on the rest.  The lists take 4 KB more than the rings did, out of the Bloom array.  cfg3
+// 2.815 -> 2.746 ms per 4 GiB, word soup -5 %, 22.07 -> 21.38 VALU per byte (profiles/r07_gram4_decomposition.txt, r07_gram4_pmc_sq.txt).
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 
 #include "device_tables.hpp"
 #include "gram4_filter.hpp"
@@ -36,7 +41,7 @@ namespace daac {
 namespace {
 
 typedef uint32_t g4_u32x4_t __attribute__((ext_vector_type(4)));
-constexpr uint32_t kRing4 = 128;        // entries of a wave's hit queue (FIFO; at most 63 left over + 64 new), u16 each: the hit byte's offset in the wave's text slot
+constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the hit byte's offset in the wave's text slot
 constexpr uint32_t kProbePercent4 = 3;  // density probe: TAIL when more than 3 % of the sampled positions start a walker
 typedef __attribute__((address_space(3))) const uint32_t lds4_cu32;
 typedef __attribute__((address_space(3))) uint32_t lds4_u32;
@@ -60,6 +65,23 @@ __device__ __forceinline__ uint32_t wave_shr1_4(uint32_t v, uint32_t lane0) {
     uint32_t d = lane0;
     asm volatile("s_nop 1\nv_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(v));
     return d;
+}
+// inclusive sum over lanes 0 .. lane: four row shifts, two row broadcasts (a lane whose source is outside its row or whose row is
+// masked off adds the 0 it was given as `old`)
+__device__ __forceinline__ uint32_t g4_wave_scan(uint32_t v) {
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, false));   // row_shr:1
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, false));   // row_shr:2
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, false));   // row_shr:4
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, false));   // row_shr:8
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));   // row_bcast:15 (rows 1, 3)
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x143, 0xc, 0xf, false));   // row_bcast:31 (rows 2, 3)
+    return v;
+}
+// f(integral_constant<int, 0>), f(.. 1>), .. while f returns true: a loop unrolled by hand (the compiler keeps a loop with a ballot in its
+// exit test rolled)
+template <typename F, int... I>
+__device__ __forceinline__ void g4_turns(F &&f, std::integer_sequence<int, I...>) {
+    (void)(... && f(std::integral_constant<int, I>{}));
 }
 __device__ __forceinline__ unsigned long long g4_wave_sum(unsigned long long v) {
 #pragma unroll
@@ -120,10 +142,9 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     const uint32_t ub4 = g.unused_byte * 0x01010101u;
     const uint8_t *__restrict__ hay = a.hay_al;
     const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
-    // per-wave LDS: the text slot; the hit queues of all waves come first (each starts at a multiple of its size)
+    // per-wave LDS: the text slot; the hit lists of all waves come first
     const uint32_t tb = L.off_wave + wave_in_wg * L.wave_stride;   // wave-uniform
-    const uint32_t ringb = wave_in_wg * (kRing4 * 2u);
-    const uint32_t ringb_v = pin4(ringb);   // (the same in a vector register, for the queue store's v_and_or_b32: one scalar / literal operand per VOP3)
+    const uint32_t listb = wave_in_wg * (kList4 * 2u);
     // this wave's slab of pending walkers, 16-byte entries.  plain: {position of the hit byte, hit record x, hit record y, the four text
     // bytes behind the hit}; TAIL: {position, state | class << 27, text bytes from position + 2 on, three more | how many << 24}
     const uint64_t slab_index = (static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave_in_wg) * a.wq_slab;
@@ -232,8 +253,8 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         wq_n = 0;
     };
 
-    // ---- the hit queue: entry = offset of the hit byte from the start of the wave's text slot (u16)
-    uint32_t q_head = 0, q_tail = 0;   // wave-uniform, free running; entries live at (index & (kRing4 - 1))
+    // ---- the hit list: entry = offset of the hit byte from the start of the wave's text slot (u16)
+    uint32_t q_head = 0, q_tail = 0;   // wave-uniform: entries [q_head, q_tail) of the list are queued, not yet taken
     uint32_t posbias = 0;              // (virtual position of a byte - epoch_base) - (its LDS address), of the text in the slot
     uint32_t st_n = 0;                 // wave-uniform: lanes [0, st_n) hold an entry of the NEXT batch already taken out of queue and slot
     uint32_t pend_lo = 0;              // the bytes p-3 .. p of the next batch's entry (p = its hit byte); pend_pos / pend_t0 / pend_t1 go with it
@@ -329,11 +350,11 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             p2_t1 = pend_t1 >> 8;
         }
     };
-    // Takes `cnt` entries from the head of the queue into lanes [first, first + cnt): position, the four bytes up to the hit byte, the
+    // Takes `cnt` entries from the head of the list into lanes [first, first + cnt): position, the four bytes up to the hit byte, the
     // four (TAIL: eight) behind it.  After this the entries no longer refer to the slot.
     auto derive = [&](uint32_t first, uint32_t cnt) {
         if (lane - first < cnt) {
-            const uint32_t e = tb + *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(ringb | (((q_head + lane - first) << 1) & (kRing4 * 2u - 2u))));
+            const uint32_t e = tb + *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(listb + ((q_head + lane - first) << 1)));
             pend_pos = e + posbias;
             const uint32_t t3 = e - 3u;
             const uint32_t a0 = t3 & ~3u, sh = t3 & 3u;
@@ -486,6 +507,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 derive(st_n, n_left);
                 st_n += n_left;
             }
+            q_head = q_tail = 0;
             const uint32_t slot = tb;                             // wave-uniform
             const uint32_t my_text = slot + 16u + lane * P;       // LDS address of this lane's first byte
             posbias = static_cast<uint32_t>(sb - epoch_base) - (slot + 16u);
@@ -550,28 +572,41 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             }
             cnt32 += ccnt;
 
-            // ---- queue the hits, one per lane and turn ----
-            const uint32_t text_adj = my_text - (32u - P) - tb;   // (queue entries are offsets in the wave's slot: 16 bits)
+            // ---- queue the hits: a wave prefix sum of the lanes' hit counts gives each lane the list index of its first one, every lane
+            // then writes its own in turns (5 VALU a turn; one ballot, two mbcnt and the slot's address in every turn cost 9 before), and
+            // batches of 64 are cut from the list once the step's hits are in.  A pass queues what fits; the rest waits for the next ----
+            const uint32_t text_adj = my_text - (32u - P) - tb;   // (list entries are offsets in the wave's slot: 16 bits)
             for (;;) {
-                const bool has = H != 0;
-                const unsigned long long m = __ballot(has);
-                if (m == 0) break;
-                // every lane computes (an idle lane's entry is never stored); the ring of a wave starts at a multiple of its size
-                uint32_t b;
-                asm("v_ffbl_b32 %0, %1" : "=v"(b) : "v"(H));   // (all lanes: -1 where there is no bit)
-                const uint32_t entry = text_adj + b;
-                H &= H - 1u;
-                // slot = ((q_tail + lanes with a hit below this one) * 2 & ring mask) | ring base, in four instructions: the two mbcnt, one
-                // add-and-shift with q_tail as the scalar operand, one and-or (left to itself the compiler moves q_tail into a register for
-                // mbcnt's accumulator — both of mbcnt_lo's other operands are scalar already — and splits the and-or: six; this loop turns
-                // 9.5 times per step)
-                const uint32_t below_me = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-                uint32_t at2, slot_addr;
-                asm("v_add_lshl_u32 %0, %1, %2, 1" : "=v"(at2) : "v"(below_me), "s"(q_tail));
-                asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(slot_addr) : "v"(at2), "s"(kRing4 * 2u - 2u), "v"(ringb_v));   // (VOP3 takes no literal on gfx950: the mask is a scalar register)
-                if (has) *reinterpret_cast<lds4_u16 *>(static_cast<uintptr_t>(slot_addr)) = static_cast<uint16_t>(entry);
-                q_tail += static_cast<uint32_t>(__popcll(m));
-                if (st_n + q_tail - q_head >= 64u) process_batch(64u);
+                if (__ballot(H != 0u) == 0) break;   // (sparse text: most steps have no hit and skip the scan)
+                const uint32_t n = __popc(H);
+                const uint32_t incl = g4_wave_scan(n);
+                const uint32_t tot = __builtin_amdgcn_readlane(incl, 63);
+                const uint32_t first = q_tail + incl - n;   // list index of this lane's first hit
+                const uint32_t room = first < kList4 ? kList4 - first : 0u;
+                const uint32_t lim = n < room ? n : room;   // hits this lane queues in this pass (the rest stay in H)
+                const uint32_t at = pin4(listb + (first << 1));   // (pinned: the compiler would add the base again inside every turn)
+                g4_turns([&](auto tc) -> bool {   // turn t: the lanes with more than t hits to queue write their next one at `at` + 2 t
+                    constexpr uint32_t t = decltype(tc)::value;
+                    const bool w = t < lim;
+                    if (__ballot(w) == 0) return false;
+                    if (w) {
+                        *reinterpret_cast<lds4_u16 *>(static_cast<uintptr_t>(at + 2u * t)) = static_cast<uint16_t>(text_adj + __builtin_ctz(H));
+                        H &= H - 1u;
+                    }
+                    return true;
+                }, std::make_integer_sequence<int, P>{});
+                const uint32_t in = std::min(tot, kList4 - q_tail);
+                q_tail += in;
+                while (st_n + q_tail - q_head >= 64u) process_batch(64u);
+                if (in == tot) break;
+                // more hits than the list holds: the fewer than 64 entries left move to its front and the scan runs again
+                const uint32_t n_left = q_tail - q_head;
+                if (lane < n_left) {
+                    const uint16_t v = *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(listb + ((q_head + lane) << 1)));
+                    *reinterpret_cast<lds4_u16 *>(static_cast<uintptr_t>(listb + (lane << 1))) = v;
+                }
+                q_head = 0;
+                q_tail = n_left;
             }
         }
         tot_cnt += cnt32;  // per region: 32 bits cannot overflow within one
@@ -683,7 +718,7 @@ bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, b
     if (rfull && dev.rfull == nullptr) return false;
     const uint32_t slot = 64u * ppl + 32u;
     L.wave_stride = slot;
-    L.off_wave = waves * kRing4 * 2u;      // the hit queues sit at 0
+    L.off_wave = waves * kList4 * 2u;      // the hit lists sit at 0
     L.threads = waves * 64u;
     L.arith = (want_arith && dev.arith) ? 1u : 0u;
     const uint32_t per_wg = L.off_wave + waves * L.wave_stride;
@@ -706,7 +741,7 @@ bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, b
     return L.lds_bytes <= lds_limit;
 }
 uint32_t gram4_filter_room(uint32_t m_bytes, uint32_t sdir_bytes, bool arith, uint32_t lds_limit) {
-    const uint32_t fixed = 16u * kRing4 * 2u + 16u * (64u * 32u + 32u) + (arith ? 0u : 256u) + sdir_bytes + m_bytes;
+    const uint32_t fixed = 16u * kList4 * 2u + 16u * (64u * 32u + 32u) + (arith ? 0u : 256u) + sdir_bytes + m_bytes;
     return fixed < lds_limit ? (lds_limit - fixed) & ~15u : 0u;
 }
 
