@@ -26,6 +26,12 @@
 // a turn instead of 9 (ballot, two mbcnt and a ring address every turn), batches of 64 cut once the step's hits are in; a step with more
 // hits than the list holds runs the scan again on the rest.  The lists take 4 KB more than the rings did, out of the Bloom array.  cfg3
 // 2.815 -> 2.746 ms per 4 GiB, word soup -5 %, 22.07 -> 21.38 VALU per byte (profiles/r07_gram4_decomposition.txt, r07_gram4_pmc_sq.txt).
+// Round 8: fewer instructions per hit on the FILT path (profiles/r08_gram4_*.txt): the probe's word index is one v_mul_hi_u32_u24 and the
+// ENDS rotation reads h's low bits as they are (gram4_filter.hpp); survivors that fail the probe all permute to one spare lane; rank_and_ask
+// takes an ARITH hit's classes as byte - lo (a hit's bytes are pattern bytes: no min) and masks the group's words with one v_bfe_i32 each.
+// Dropped: `derive` by two unaligned ds_read_b32 (five VALU fewer a batch, but an unaligned read is 7x slower than the aligned ones,
+// tools/micro/lds_unaligned.hip).  Not done: survivors carrying a packed context index (the class work would move to every hit, 3.65 batches
+// a step, from 1.6 survivor batches) and a finer coarse directory (its LDS comes out of the Bloom array).
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -358,7 +364,8 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             pend_pos = e + posbias;
             const uint32_t t3 = e - 3u;
             const uint32_t a0 = t3 & ~3u, sh = t3 & 3u;
-            // the dwords around the hit byte (the slot is self-contained: never outside [slot + 12, slot + SLOT))
+            // the dwords around the hit byte (the slot is self-contained: never outside [slot + 12, slot + SLOT)).  (Round 8 tried two
+            // ds_read_b32 at the byte address instead: 7x slower than these reads on gfx950, tools/micro/lds_unaligned.hip)
             const uint32_t d0 = lds_u32(a0), d1 = lds_u32(a0 + 4u), d2 = lds_u32(a0 + 8u);
             pend_lo = __builtin_amdgcn_alignbyte(d1, d0, sh);              // bytes p-3 .. p
             pend_t0 = __builtin_amdgcn_alignbyte(d2, d1, sh);              // bytes p+1 .. p+4
@@ -370,10 +377,21 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         q_head += cnt;
     };
     // rank of the hit whose bytes p-3 .. p are x_lo -> its record asked for (into `pend`)
+    // (ARITH: the K+1 bytes of a hit are all pattern bytes, so their classes are byte - lo without the min — the context index is two
+    // multiply-adds of selected bytes with the bias folded in, round 8)
+    const uint32_t lo_idx = K == 3 ? lo * (C * C + C + 1u) : lo * (C + 1u);
     auto rank_and_ask = [&](uint32_t x_lo) {
-        const uint32_t c1 = cls_of((x_lo >> 8) & 0xffu), c2 = cls_of((x_lo >> 16) & 0xffu), d = cls_of(x_lo >> 24);
-        uint32_t idx = __umul24(c1, C) + c2;
-        if (K == 3) idx = __umul24(cls_of(x_lo & 0xffu), C * C) + idx;
+        uint32_t idx, d;
+        if (ARITH) {
+            idx = mad24((x_lo >> 8) & 0xffu, C, ((x_lo >> 16) & 0xffu) - lo_idx);
+            if (K == 3) idx = mad24(x_lo & 0xffu, C * C, idx);
+            d = (x_lo >> 24) - lo;
+        } else {
+            const uint32_t c1 = cls_of((x_lo >> 8) & 0xffu), c2 = cls_of((x_lo >> 16) & 0xffu);
+            d = cls_of(x_lo >> 24);
+            idx = __umul24(c1, C) + c2;
+            if (K == 3) idx = __umul24(cls_of(x_lo & 0xffu), C * C) + idx;
+        }
         // rank of continuation bit d of that M word among all set bits = offset of the depth-(K+1) state
         const uint32_t am = (idx << 2) + offM;
         const uint32_t own = lds_u32(am);
@@ -382,15 +400,20 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             const uint32_t base = *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>((idx << 1) + offS));
             rank = base + __popc(own & below(d));
         } else {
-            const uint32_t grp = offM + ((idx & ~3u) << 2);
+            const uint32_t grp = am & ~15u;   // (M starts 16-byte aligned)
             const uint32_t qx = lds_u32(grp), qy = lds_u32(grp + 4u), qz = lds_u32(grp + 8u);
-            const uint32_t sub = idx & 3u;
-            const uint32_t base = DIR == 1 ? *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(offS + ((idx >> 2) << 1)))
-                                           : *reinterpret_cast<lds4_cu32 *>(static_cast<uintptr_t>(offS + ((idx >> 2) << 2)));
+            const uint32_t gi = pin4(idx >> 2);   // (pinned: one v_lshl_add_u32 below, not a shift, a mask and an add)
+            const uint32_t base = DIR == 1 ? *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>((gi << 1) + offS))
+                                           : *reinterpret_cast<lds4_cu32 *>(static_cast<uintptr_t>((gi << 2) + offS));
+            // word j of the group counts when it lies before the hit's, i.e. bit idx & 3 of 0b1110 / 0b1100 / 0b1000 is set: one v_bfe_i32
+            // of the nibble repeated eight times, at offset idx (the instruction reads bits 4:0 of the offset) gives all ones or zero
+            const uint32_t mx = static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(0xEEEEEEEEu), idx, 1u));
+            const uint32_t my = static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(0xCCCCCCCCu), idx, 1u));
+            const uint32_t mz = static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(0x88888888u), idx, 1u));
             uint32_t under = __popc(own & below(d));
-            under += sub > 0 ? __popc(qx & 0x3fffffffu) : 0u;
-            under += sub > 1 ? __popc(qy & 0x3fffffffu) : 0u;
-            under += sub > 2 ? __popc(qz & 0x3fffffffu) : 0u;
+            under += __popc(qx & mx & 0x3fffffffu);
+            under += __popc(qy & my & 0x3fffffffu);
+            under += __popc(qz & mz & 0x3fffffffu);
             rank = base + under;
         }
         if (TAIL) {
@@ -417,13 +440,17 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             // first stage: the probe of gram4_filter.hpp on the raw bytes p-K .. p and p + 1 — one word, the GO key's two bits or the ENDS key's four
             const G4Probe pr = g4f_probe(K == 3 ? pend_lo : pend_lo >> 8, pend_t0 & 0xffu, bloomW);
             const uint32_t fw = lds_u32(offB + (pr.word << 2));
-            const bool pass = lane < n && ((fw & pr.go) == pr.go || (fw & pr.ends) == pr.ends);
-            const unsigned long long pm = __ballot(pass);
+            const bool pass = lane < n && ((pr.go & ~fw) == 0u || (pr.ends & ~fw) == 0u);
+            const unsigned long long pm = __builtin_amdgcn_ballot_w64(pass);
             if (pm != 0) {
-                // survivors move to lanes sb_n, sb_n + 1, .. (mod 64) — one forward permute per word, the others fill the lanes in between —
+                // survivors move to lanes sb_n, sb_n + 1, .. (mod 64) — one forward permute per word; the others all go to lane sb_n - 1 (mod 64),
+                // which is outside [sb_n, sb_n + s) unless all 64 pass, and whose value is not looked at (round 8: before, they filled the lanes in
+                // between, three VALU more) —
                 const uint32_t s = static_cast<uint32_t>(__popcll(pm));
                 const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(pm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(pm), 0));
-                const uint32_t tgt = ((pass ? sb_n + r : sb_n + s + lane - r) & 63u) << 2;
+                uint32_t t;   // rank among the survivors, 63 for the others (the ballot as the mask: left to itself the compiler branches on it)
+                asm("v_cndmask_b32_e64 %0, 63, %1, %2" : "=v"(t) : "v"(r), "s"(pm));
+                const uint32_t tgt = ((t + sb_n) << 2) & 0xfcu;
                 const uint32_t r_pos = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_pos)));
                 const uint32_t r_lo = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_lo)));
                 const uint32_t r_t0 = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_t0)));
