@@ -146,6 +146,32 @@ class DeviceMatches:
             pass
 
 
+class DeviceOffsets:
+    """`count` u64 at device address `ptr` (the CSR offsets of a batch's tuple list)"""
+
+    def __init__(self, ptr, count):
+        self.ptr, self.count = ptr, count
+
+    def to_numpy(self):
+        out = np.zeros(self.count, dtype=np.uint64)
+        if self.count:
+            if not self.ptr:
+                raise DaachorseError(1, "the device offsets have been freed")
+            _ffi.check(_ffi.lib().daac_device_to_host(out.ctypes.data, self.ptr, self.count * 8))
+        return out
+
+    def free(self):
+        if self.ptr:
+            _ffi.lib().daac_device_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class _LazyIter:
     """Iterator<Item = Match<u32>> over daac_iter_* (bytewise/iter.rs next())."""
 
@@ -423,6 +449,108 @@ class DoubleArrayAhoCorasick:
         _ffi.check(_ffi.lib().daac_scan_count_range(self._h, int(mode), int(engine), h.ptr, h.len, begin, h.is_device, stream,
                                                     C.byref(cnt), C.byref(cs), None))
         return cnt.value, cs.value
+
+    # ---- batches: many documents in one call, per-document results (daac_scan_count_batch / daac_scan_batch_device16) ------------
+    # `docs`: a sequence of str / bytes / uint8 arrays (packed on the host), or (uint8 CUDA tensor, int64 CUDA tensor of n + 1 offsets).
+    # Every document gets what the single-haystack call returns on it alone; positions are relative to the document.
+    def _count_batch(self, mode, docs, engine, stream, want_checksum, out):
+        b = _Batch(docs)
+        if out is not None:   # device results: the call is asynchronous on `stream`
+            outs = out if isinstance(out, (tuple, list)) else (out,)
+            cp = _device_u64(outs[0], b.n)
+            sp = _device_u64(outs[1], b.n) if want_checksum else None
+            _ffi.check(_ffi.lib().daac_scan_count_batch(self._h, int(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream, cp, sp, 1))
+            return None
+        counts = np.zeros(b.n, dtype=np.uint64)
+        sums = np.zeros(b.n, dtype=np.uint64) if want_checksum else None
+        _ffi.check(_ffi.lib().daac_scan_count_batch(self._h, int(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream,
+                                                    counts.ctypes.data if b.n else None,
+                                                    sums.ctypes.data if want_checksum and b.n else None, 0))
+        return (counts, sums) if want_checksum else counts
+
+    def count_batch(self, mode, docs, engine=Engine.Auto, stream=None, out=None):
+        """-> np.uint64[n]: `.count()` of every document; with `out` (a CUDA int64 tensor of n) the counts stay there (asynchronous)"""
+        return self._count_batch(mode, docs, engine, stream, False, out)
+
+    def scan_count_batch(self, mode, docs, engine=Engine.Auto, stream=None, out=None):
+        """-> (counts, checksums), np.uint64[n] each (the checksum of scan_count, ends relative to the document); with `out` =
+        (counts tensor, checksums tensor) on the device the results stay there (asynchronous)"""
+        return self._count_batch(mode, docs, engine, stream, True, out)
+
+    def scan_batch_device(self, mode, docs, engine=Engine.Auto, stream=None):
+        """-> (DeviceMatches of 16-byte tuples {end, length, value}, DeviceOffsets: n + 1 u64 CSR offsets on the device): document i's
+        tuples are [offsets[i], offsets[i+1]).  Both are freed with .free() (or when they are collected)."""
+        b = _Batch(docs)
+        ptr, offs, tot = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_scan_batch_device16(self._h, int(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream,
+                                                       C.byref(ptr), C.byref(offs), C.byref(tot)))
+        return DeviceMatches(ptr.value, tot.value, MATCH16_DTYPE), DeviceOffsets(offs.value, b.n + 1)
+
+    def scan_batch(self, mode, docs, engine=Engine.Auto, stream=None):
+        """-> (MATCH_DTYPE array, start / end / value relative to each document, np.uint64[n + 1] offsets into it)"""
+        dm, do = self.scan_batch_device(mode, docs, engine, stream)
+        try:
+            t16 = dm.to_numpy()
+            offsets = do.to_numpy()
+        finally:
+            dm.free()
+            do.free()
+        out = np.zeros(len(t16), dtype=MATCH_DTYPE)
+        out["end"] = t16["end"]
+        out["start"] = t16["end"] - t16["length"].astype(np.uint64)
+        out["value"] = t16["value"]
+        return out, offsets
+
+
+class _Batch:
+    """A batch argument: a sequence of documents (str / bytes / uint8 arrays), packed into one host buffer + n + 1 offsets, or a pair
+    (uint8 CUDA tensor, int64 CUDA tensor of n + 1 offsets) that stays on the device."""
+
+    def __init__(self, docs):
+        if isinstance(docs, tuple) and len(docs) == 2 and hasattr(docs[0], "data_ptr") and hasattr(docs[1], "data_ptr"):
+            hay, off = docs
+            if not (hay.is_cuda and off.is_cuda):
+                raise DaachorseError(1, "a device batch is (uint8 CUDA tensor, int64 CUDA offsets tensor)")
+            if hay.dtype.itemsize != 1 or not hay.is_contiguous() or off.dtype.itemsize != 8 or not off.is_contiguous() or off.dim() != 1 or off.numel() < 1:
+                raise DaachorseError(1, "a device batch is (contiguous uint8 tensor, contiguous int64 tensor of n + 1 offsets)")
+            if hay.numel() == 0:   # (documents that are all empty still need a buffer to point at)
+                hay = _one_granule(hay)
+            self.keep = (hay, off)
+            self.hay = hay.data_ptr()
+            self.off = off.data_ptr()
+            self.n = off.numel() - 1
+            self.is_device = 1
+            return
+        parts = []
+        for d in docs:
+            if isinstance(d, np.ndarray):
+                if d.dtype.itemsize != 1:
+                    raise DaachorseError(1, "a document array must have a 1-byte dtype (uint8)")
+                parts.append(np.ascontiguousarray(d).view(np.uint8).tobytes())
+            else:
+                parts.append(_as_bytes(d))
+        self.offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            self.offsets[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        self.buf = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8)
+        self.keep = None
+        self.hay = self.buf.ctypes.data
+        self.off = self.offsets.ctypes.data
+        self.n = len(parts)
+        self.is_device = 0
+
+
+def _one_granule(t):
+    """a 16-byte device buffer next to tensor t"""
+    import torch
+    return torch.zeros(16, dtype=torch.uint8, device=t.device)
+
+
+def _device_u64(out, n):
+    """(pointer, tensor) of a CUDA tensor of n 8-byte elements, for results left on the device"""
+    if not (hasattr(out, "data_ptr") and out.is_cuda and out.dtype.itemsize == 8 and out.is_contiguous() and out.numel() >= n):
+        raise DaachorseError(1, "device results go to a contiguous CUDA tensor of n int64 / uint64 elements")
+    return out.data_ptr()
 
 
 def scan_count_multi(pma, mode, shards, engine=Engine.Auto, checksum=True):

@@ -1,0 +1,408 @@
+// C ABI (include/daachorse_amd.h), part 6: batches — many independent documents in one call (daac_scan_count_batch,
+// daac_scan_batch_device16).  The kernels are batch_kernels.hip; this file validates, stages host haystacks in windows of whole
+// documents, routes the documents the chain modes cannot give one lane to the single-haystack path, and assembles the results.
+#include "api_internal.hpp"
+#include "batch.hpp"
+
+namespace {
+
+constexpr uint64_t kBatchWindow = 256ull << 20;  // host haystacks: bytes staged to the device at a time (whole documents)
+constexpr unsigned long long kNone = ~0ull;
+
+struct BatchPlan {
+    bool chain = false, leftmost = false, heads = false, tier = false;
+    uint64_t piece = 4096, lane_max = 16384;
+    uint32_t halo = 0, threads = 1024;
+};
+
+// the engine rules of the single-haystack calls (make_plan), and the batch's own: GRAM and PFX do not serve batches
+daac_status batch_engine(const daac_pma *pma, const DeviceTables *t, int mode, int engine, BatchPlan &bp) {
+    bp.chain = mode == DAAC_FIND || mode == DAAC_LEFTMOST_FIND;
+    bp.leftmost = mode == DAAC_LEFTMOST_FIND;
+    bp.heads = mode == DAAC_FIND_OVERLAPPING_NO_SUFFIX;
+    if (engine != DAAC_ENGINE_AUTO && engine != DAAC_ENGINE_TIERED && engine != DAAC_ENGINE_DARRAY) {
+        set_error(engine == DAAC_ENGINE_GRAM || engine == DAAC_ENGINE_PFX ? "the GRAM and PFX engines do not serve batches (engine AUTO, TIERED or DARRAY)"
+                                                                          : "unknown engine");
+        return DAAC_ERR_UNSUPPORTED;
+    }
+    if (pma->charwise && engine == DAAC_ENGINE_TIERED) {
+        set_error("charwise automata run on their double array only (engine AUTO or DARRAY)");
+        return DAAC_ERR_UNSUPPORTED;
+    }
+    if (bp.chain && engine == DAAC_ENGINE_TIERED) {
+        set_error("find_iter / leftmost_find_iter run on the DARRAY tables only");
+        return DAAC_ERR_UNSUPPORTED;
+    }
+    if (t && engine == DAAC_ENGINE_TIERED && !t->tier_ok) {
+        set_error("TIERED engine not available for this automaton (more than 31 distinct pattern bytes, or not standard)");
+        return DAAC_ERR_UNSUPPORTED;
+    }
+    bp.tier = t && !pma->charwise && !bp.chain && (engine == DAAC_ENGINE_TIERED || (engine == DAAC_ENGINE_AUTO && t->tier_ok));
+    bp.piece = static_cast<uint64_t>(std::max<int64_t>(64, OPT(batch_piece)));
+    bp.lane_max = static_cast<uint64_t>(std::min<int64_t>(std::max<int64_t>(0, OPT(batch_lane_max)), (1ll << 30) - 1));
+    bp.halo = pma->halo();
+    uint32_t threads = static_cast<uint32_t>(OPT(threads));
+    bp.threads = std::min(1024u, std::max(64u, threads & ~63u));
+    return DAAC_OK;
+}
+
+daac_status note_d(uint64_t doc) {
+    set_error("document " + std::to_string(doc) + ": the reference iterator does not terminate on it (leftmost kind, empty pattern, the document ends "
+              "inside a pattern)");
+    return DAAC_ERR_UNSUPPORTED;
+}
+
+// The arguments checked before the device is touched: statuses 1 and 5.
+daac_status batch_precheck(const daac_pma *pma, int mode, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device) {
+    if (!pma) { set_error("null handle"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    daac_status st = check_mode_kind(pma, mode);
+    if (st != DAAC_OK) return st;
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    return DAAC_OK;
+}
+
+struct Route { uint64_t pieces = 0, lane_docs = 0, long_docs = 0; };
+
+// Validates device offsets (a decreasing pair: status 1) and, for the overlapping modes, lays out the pieces: first[] (n + 1 entries,
+// first[n] = the number of pieces).  One small read-back.
+daac_status batch_layout(const BatchPlan &bp, const unsigned long long *d_off, uint64_t n, hipStream_t stream, DevBuf &layout, unsigned long long *&flags,
+                         unsigned long long *&first, uint64_t &npieces) {
+    const uint64_t m = n + 1;
+    HIP_TRY(layout.alloc((4 + (bp.chain ? 0 : m + exclusive_scan_scratch(m))) * sizeof(unsigned long long), stream));
+    flags = static_cast<unsigned long long *>(layout.p);   // [0] first decreasing offset, [1] first note D document, [2] pieces
+    first = bp.chain ? nullptr : flags + 4;
+    HIP_TRY(hipMemsetAsync(flags, 0xff, 2 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(flags + 2, 0, sizeof(unsigned long long), stream));
+    HIP_TRY(launch_batch_plan(d_off, n, bp.piece, first, flags, stream));
+    if (first) HIP_TRY(launch_exclusive_scan(first, m, flags + 2, first + m, stream));
+    unsigned long long *pin = reinterpret_cast<unsigned long long *>(pinned_words());
+    unsigned long long local[3];
+    unsigned long long *h = pin ? pin : local;
+    HIP_TRY(hipMemcpyAsync(h, flags, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h[0] != kNone) { set_error("offsets decrease at document " + std::to_string(h[0])); return DAAC_ERR_INVALID_ARGUMENT; }
+    npieces = h[2];
+    return DAAC_OK;
+}
+
+// the documents the chain modes send through the single-haystack path
+daac_status long_docs(const BatchPlan &bp, const unsigned long long *d_off, const uint64_t *h_off, uint64_t n, hipStream_t stream,
+                      std::vector<uint64_t> &off_host, std::vector<uint64_t> &longs) {
+    if (!h_off) {
+        off_host.resize(n + 1);
+        HIP_TRY(hipMemcpyAsync(off_host.data(), d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        h_off = off_host.data();
+    } else {
+        off_host.assign(h_off, h_off + n + 1);
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_off[i + 1] - h_off[i] > bp.lane_max) longs.push_back(i);
+    return DAAC_OK;
+}
+
+// counts[i] (and checksums[i]) of documents [0, n) of a device haystack; counts / checksums are device arrays
+daac_status count_window(daac_pma *pma, DeviceTables *t, const BatchPlan &bp, int mode, int engine, const uint8_t *hay, const unsigned long long *d_off,
+                         const uint64_t *h_off, uint64_t n, hipStream_t stream, unsigned long long *counts, unsigned long long *checksums, Route &route) {
+    DevBuf layout;
+    unsigned long long *flags = nullptr, *first = nullptr;
+    uint64_t npieces = 0;
+    daac_status st = batch_layout(bp, d_off, n, stream, layout, flags, first, npieces);
+    if (st != DAAC_OK) return st;
+    BatchArgs a{};
+    a.hay = hay;
+    a.off = d_off;
+    a.n = n;
+    a.first_piece = first;
+    a.npieces = npieces;
+    a.piece_bytes = bp.piece;
+    a.halo = bp.halo;
+    a.lane_max = bp.lane_max;
+    a.flags = flags;
+    DevBuf res;
+    if (!bp.chain) {
+        HIP_TRY(res.alloc(3 * std::max<uint64_t>(npieces, 1) * sizeof(unsigned long long), stream));
+        a.res = static_cast<unsigned long long *>(res.p);
+        HIP_TRY(launch_batch_pieces(bp.tier ? &t->tier : nullptr, (!bp.tier && !pma->charwise) ? &t->da : nullptr, pma->charwise ? &t->chr : nullptr, a, 0,
+                                    bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
+        HIP_TRY(launch_batch_reduce(first, a.res, n, counts, checksums, stream));
+        route.pieces += npieces;
+        route.lane_docs += n;
+        return DAAC_OK;
+    }
+    std::vector<uint64_t> off_host, longs;
+    if ((st = long_docs(bp, d_off, h_off, n, stream, off_host, longs)) != DAAC_OK) return st;
+    HIP_TRY(res.alloc(3 * std::max<uint64_t>(n, 1) * sizeof(unsigned long long), stream));
+    a.res = static_cast<unsigned long long *>(res.p);
+    HIP_TRY(hipMemsetAsync(a.res, 0, 3 * n * sizeof(unsigned long long), stream));
+    HIP_TRY(launch_batch_chain(pma->charwise ? nullptr : &t->da, pma->charwise ? &t->chr : nullptr, a, 0, bp.leftmost, static_cast<uint32_t>(t->num_cu), stream));
+    uint64_t first_d = kNone;
+    for (uint64_t i : longs) {   // (each call settles its chain and synchronises: about a call's overhead per document)
+        const uint64_t b = off_host[i], len = off_host[i + 1] - b;
+        st = daac_scan_count_range(pma, mode, engine, hay + b, len, 0, 1, stream, nullptr, nullptr, reinterpret_cast<uint64_t *>(a.res + 3 * i));
+        if (st == DAAC_ERR_UNSUPPORTED && bp.leftmost && pma->root_has_output()) { first_d = i; break; }
+        if (st != DAAC_OK) return st;
+    }
+    HIP_TRY(launch_batch_reduce(nullptr, a.res, n, counts, checksums, stream));
+    if (bp.leftmost && pma->root_has_output()) {   // the one request with a document on which the reference does not end
+        unsigned long long f = kNone;
+        HIP_TRY(hipMemcpyAsync(&f, flags + 1, sizeof(f), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (std::min<uint64_t>(f, first_d) != kNone) return note_d(std::min<uint64_t>(f, first_d));
+    }
+    route.lane_docs += n - longs.size();
+    route.long_docs += longs.size();
+    return DAAC_OK;
+}
+
+// All tuples of documents [0, n) of a device haystack as one CSR list: *list (16-byte tuples, ends relative to the document), *doc_off
+// (n + 1 entries, device), *total.
+daac_status tuples_window(daac_pma *pma, DeviceTables *t, const BatchPlan &bp, int mode, int engine, const uint8_t *hay, const unsigned long long *d_off,
+                          const uint64_t *h_off, uint64_t n, hipStream_t stream, void **list, unsigned long long **doc_off, uint64_t *total, Route &route) {
+    *list = nullptr;
+    *doc_off = nullptr;
+    *total = 0;
+    DevBuf layout;
+    unsigned long long *flags = nullptr, *first = nullptr;
+    uint64_t npieces = 0;
+    daac_status st = batch_layout(bp, d_off, n, stream, layout, flags, first, npieces);
+    if (st != DAAC_OK) return st;
+    BatchArgs a{};
+    a.hay = hay;
+    a.off = d_off;
+    a.n = n;
+    a.first_piece = first;
+    a.npieces = npieces;
+    a.piece_bytes = bp.piece;
+    a.halo = bp.halo;
+    a.lane_max = bp.lane_max;
+    a.flags = flags;
+    // counts per piece (overlapping) or per document (chain), n + 1 / npieces + 1 of them: their exclusive scan is the CSR layout
+    const uint64_t units = bp.chain ? n : npieces;
+    DevBuf cnt;
+    HIP_TRY(cnt.alloc((units + 4 + exclusive_scan_scratch(units + 1)) * sizeof(unsigned long long), stream));
+    a.counts = static_cast<unsigned long long *>(cnt.p);
+    unsigned long long *d_total = a.counts + units + 1;
+    HIP_TRY(hipMemsetAsync(a.counts, 0, (units + 2) * sizeof(unsigned long long), stream));
+    const TierDev *tier = bp.tier ? &t->tier : nullptr;
+    const DArrayDev *da = (!bp.tier && !pma->charwise) ? &t->da : nullptr;
+    const CharDev *chr = pma->charwise ? &t->chr : nullptr;
+    std::vector<uint64_t> off_host, longs;
+    std::vector<api::DevMatches> long_lists;
+    std::vector<unsigned long long> long_counts;
+    if (!bp.chain) {
+        HIP_TRY(launch_batch_pieces(tier, da, chr, a, 1, bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
+    } else {
+        if ((st = long_docs(bp, d_off, h_off, n, stream, off_host, longs)) != DAAC_OK) return st;
+        HIP_TRY(launch_batch_chain(da, chr, a, 1, bp.leftmost, static_cast<uint32_t>(t->num_cu), stream));
+        long_lists = std::vector<api::DevMatches>(longs.size());
+        long_counts.resize(longs.size());
+        uint64_t first_d = kNone;
+        for (size_t k = 0; k < longs.size(); ++k) {   // materialised first: their counts enter the scan
+            const uint64_t i = longs[k], b = off_host[i], len = off_host[i + 1] - b;
+            st = scan_range_device(pma, t, mode, engine, hay + b, 0, len, len, stream, long_lists[k], nullptr);
+            if (st == DAAC_ERR_UNSUPPORTED && bp.leftmost && pma->root_has_output()) { first_d = i; break; }
+            if (st != DAAC_OK) return st;
+            long_counts[k] = long_lists[k].n;
+            HIP_TRY(hipMemcpyAsync(a.counts + i, &long_counts[k], sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+        }
+        if (bp.leftmost && pma->root_has_output()) {
+            unsigned long long f = kNone;
+            HIP_TRY(hipMemcpyAsync(&f, flags + 1, sizeof(f), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (std::min<uint64_t>(f, first_d) != kNone) return note_d(std::min<uint64_t>(f, first_d));
+        }
+    }
+    HIP_TRY(launch_exclusive_scan(a.counts, units + 1, d_total, d_total + 3, stream));
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (tot * 16 > static_cast<unsigned long long>(OPT(max_result_bytes))) {
+        set_error("match list of " + std::to_string(tot) + " tuples exceeds max_result_bytes");
+        return DAAC_ERR_AUTOMATON_SCALE;
+    }
+    void *out = nullptr;
+    unsigned long long *doffs = nullptr;
+    HIP_TRY(dev_malloc(&out, std::max<uint64_t>(tot, 1) * 16, stream));
+    std::unique_ptr<void, std::function<void(void *)>> out_guard(out, [stream](void *p) { dev_free(p, stream); });
+    HIP_TRY(dev_malloc(reinterpret_cast<void **>(&doffs), (n + 1) * sizeof(unsigned long long), stream));
+    std::unique_ptr<void, std::function<void(void *)>> off_guard(doffs, [stream](void *p) { dev_free(p, stream); });
+    a.out = static_cast<uint4 *>(out);
+    if (!bp.chain) {
+        if (tot) HIP_TRY(launch_batch_pieces(tier, da, chr, a, 2, bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
+        HIP_TRY(launch_batch_doc_offsets(first, a.counts, n, d_total, doffs, stream));
+        route.pieces += npieces;
+        route.lane_docs += n;
+    } else {
+        if (tot) HIP_TRY(launch_batch_chain(da, chr, a, 2, bp.leftmost, static_cast<uint32_t>(t->num_cu), stream));
+        HIP_TRY(hipMemcpyAsync(doffs, a.counts, (n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+        if (!longs.empty()) {   // the long documents' lists into their CSR slots
+            std::vector<unsigned long long> at(n + 1);
+            HIP_TRY(hipMemcpyAsync(at.data(), a.counts, (n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            for (size_t k = 0; k < longs.size(); ++k) {
+                api::DevMatches &dm = long_lists[k];
+                if (dm.n == 0) continue;
+                void *dst = static_cast<char *>(out) + at[longs[k]] * 16;
+                if (dm.f16_done) HIP_TRY(hipMemcpyAsync(dst, dm.p, dm.n * 16, hipMemcpyDeviceToDevice, stream));
+                else HIP_TRY(launch_repack16(dm.p, dst, dm.n, stream));
+            }
+        }
+        route.lane_docs += n - longs.size();
+        route.long_docs += longs.size();
+    }
+    (void)off_guard.release();
+    *list = out_guard.release();
+    *doc_off = doffs;
+    *total = tot;
+    return DAAC_OK;
+}
+
+// Host haystacks: windows of whole documents [i0, i1) of at most kBatchWindow bytes (a longer document is a window of its own).
+template <class F>
+daac_status for_windows(const uint8_t *hay, const uint64_t *offsets, uint64_t n, hipStream_t stream, F &&fn) {
+    uint64_t i0 = 0;
+    while (i0 < n) {
+        uint64_t i1 = i0 + 1;
+        while (i1 < n && offsets[i1 + 1] - offsets[i0] <= kBatchWindow) ++i1;
+        void *staged = nullptr;
+        const uint8_t *dev_hay = nullptr;
+        daac_status st = stage_window(hay, offsets[i0], offsets[i1], stream, &staged, &dev_hay);
+        if (st != DAAC_OK) return st;
+        std::unique_ptr<void, void (*)(void *)> g(staged, [](void *p) { if (p) (void)hipFree(p); });
+        DevBuf d_off;
+        HIP_TRY(d_off.alloc((i1 - i0 + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(d_off.p, offsets + i0, (i1 - i0 + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        if ((st = fn(dev_hay, static_cast<const unsigned long long *>(d_off.p), offsets + i0, i0, i1 - i0)) != DAAC_OK) return st;
+        HIP_TRY(hipStreamSynchronize(stream));   // (the window's buffer is freed next)
+        i0 = i1;
+    }
+    return DAAC_OK;
+}
+
+void report(const BatchPlan &bp, const Route &r) {
+    g_last_engine = bp.tier ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY;
+    g_last_kernel = "batch pieces=" + std::to_string(r.pieces) + " lane_docs=" + std::to_string(r.lane_docs) + " long_docs=" + std::to_string(r.long_docs);
+}
+
+}  // namespace
+
+extern "C" {
+
+daac_status daac_scan_count_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                  void *stream_, uint64_t *counts, uint64_t *checksums, int out_is_device) {
+    PmaScope scope_(pma);
+    daac_status st = batch_precheck(pma, mode, hay, offsets, n, hay_is_device);
+    if (st != DAAC_OK) return st;
+    if (n && !counts) { set_error("counts is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    BatchPlan bp;
+    if ((st = batch_engine(pma, nullptr, mode, engine, bp)) != DAAC_OK) return st;
+    if (n == 0) { report(bp, Route{}); return DAAC_OK; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;
+    if ((st = batch_engine(pma, t, mode, engine, bp)) != DAAC_OK) return st;
+    unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(counts), *d_sums = reinterpret_cast<unsigned long long *>(checksums);
+    DevBuf outs;
+    if (!out_is_device) {
+        HIP_TRY(outs.alloc(2 * n * sizeof(unsigned long long), stream));
+        d_counts = static_cast<unsigned long long *>(outs.p);
+        d_sums = checksums ? d_counts + n : nullptr;
+    }
+    Route route;
+    if (hay_is_device) {
+        st = count_window(pma, t, bp, mode, engine, hay, reinterpret_cast<const unsigned long long *>(offsets), nullptr, n, stream, d_counts, d_sums, route);
+    } else {
+        st = for_windows(hay, offsets, n, stream, [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *h_off, uint64_t i0, uint64_t m) {
+            return count_window(pma, t, bp, mode, engine, dh, d_off, h_off, m, stream, d_counts + i0, d_sums ? d_sums + i0 : nullptr, route);
+        });
+    }
+    if (st != DAAC_OK) return st;
+    if (!out_is_device) {
+        HIP_TRY(hipMemcpyAsync(counts, d_counts, n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        if (checksums) HIP_TRY(hipMemcpyAsync(checksums, d_sums, n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    report(bp, route);
+    return DAAC_OK;
+}
+
+daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                     void *stream_, daac_match16 **dev_out, uint64_t **dev_doc_offsets, uint64_t *total) {
+    PmaScope scope_(pma);
+    daac_status st = batch_precheck(pma, mode, hay, offsets, n, hay_is_device);
+    if (st != DAAC_OK) return st;
+    if (!dev_out || !dev_doc_offsets || !total) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_out = nullptr;
+    *dev_doc_offsets = nullptr;
+    *total = 0;
+    BatchPlan bp;
+    if ((st = batch_engine(pma, nullptr, mode, engine, bp)) != DAAC_OK) return st;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) {   // one offset, 0
+        void *z = nullptr;
+        HIP_TRY(hipMalloc(&z, sizeof(uint64_t)));
+        HIP_TRY(hipMemset(z, 0, sizeof(uint64_t)));
+        *dev_doc_offsets = static_cast<uint64_t *>(z);
+        report(bp, Route{});
+        return DAAC_OK;
+    }
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;
+    if ((st = batch_engine(pma, t, mode, engine, bp)) != DAAC_OK) return st;
+    Route route;
+    void *list = nullptr;
+    unsigned long long *doc_off = nullptr;
+    uint64_t tot = 0;
+    if (hay_is_device) {
+        st = tuples_window(pma, t, bp, mode, engine, hay, reinterpret_cast<const unsigned long long *>(offsets), nullptr, n, stream, &list, &doc_off, &tot, route);
+        if (st != DAAC_OK) return st;
+    } else {
+        // every window's list, then one list: the windows' tuples back to back, their offsets shifted by the tuples before them
+        std::vector<std::pair<void *, uint64_t>> parts;
+        std::vector<uint64_t> h_doc(n + 1, 0);
+        auto free_parts = [&]() { for (auto &p : parts) dev_free(p.first, stream); parts.clear(); };
+        st = for_windows(hay, offsets, n, stream, [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *h_off, uint64_t i0, uint64_t m) {
+            void *wl = nullptr;
+            unsigned long long *wo = nullptr;
+            uint64_t wt = 0;
+            daac_status s = tuples_window(pma, t, bp, mode, engine, dh, d_off, h_off, m, stream, &wl, &wo, &wt, route);
+            if (s != DAAC_OK) return s;
+            parts.emplace_back(wl, wt);
+            std::vector<uint64_t> w(m + 1);
+            hipError_t e = hipMemcpyAsync(w.data(), wo, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            dev_free(wo, stream);
+            if (e != hipSuccess) return hip_fail(e, "batch window offsets");
+            for (uint64_t k = 0; k <= m; ++k) h_doc[i0 + k] = tot + w[k];
+            tot += wt;
+            return DAAC_OK;
+        });
+        if (st != DAAC_OK) { free_parts(); return st; }
+        hipError_t e = dev_malloc(&list, std::max<uint64_t>(tot, 1) * 16, stream);
+        if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void **>(&doc_off), (n + 1) * sizeof(uint64_t), stream);
+        uint64_t at = 0;
+        for (auto &p : parts) {
+            if (e == hipSuccess && p.second) e = hipMemcpyAsync(static_cast<char *>(list) + at * 16, p.first, p.second * 16, hipMemcpyDeviceToDevice, stream);
+            at += p.second;
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(doc_off, h_doc.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
+        free_parts();
+        if (e != hipSuccess) { dev_free(list, stream); dev_free(doc_off, stream); return hip_fail(e, "batch list assembly"); }
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (tot == 0) { dev_free(list, stream); list = nullptr; HIP_TRY(hipStreamSynchronize(stream)); }
+    *dev_out = static_cast<daac_match16 *>(list);
+    *dev_doc_offsets = reinterpret_cast<uint64_t *>(doc_off);
+    *total = tot;
+    report(bp, route);
+    return DAAC_OK;
+}
+
+}  // extern "C"

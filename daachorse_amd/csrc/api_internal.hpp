@@ -76,7 +76,9 @@ const char *last_error_cstr();
     X(find3_window, 1ll << 30, 0)        /* find3: end positions per window (tests: small windows = many restarts) */                        \
     X(workspace_keep, 8ll << 30, 0)      /* bytes of scratch a handle may keep for its emitter / find3 calls (0: none) */                    \
     X(char_map_lds, 1, 1)                /* charwise chain scans: the populated stretch of the code mapper in LDS */                         \
-    X(char_row_lds, 1, 1)                /* ... and ROOT's row of children beside it */
+    X(char_row_lds, 1, 1)                /* ... and ROOT's row of children beside it */                                                      \
+    X(batch_piece, 4096, 0)              /* batches, overlapping modes: bytes of a document per lane-piece */                                \
+    X(batch_lane_max, 16384, 0)          /* batches, chain modes: longest document one lane walks (longer: the single-haystack path) */
 
 enum OptionId : int {
 #define X(NAME, DEF, UP) OPT_##NAME,

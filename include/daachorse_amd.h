@@ -38,7 +38,9 @@ extern "C" {
  *   6 (round 6): daac_stream_feed_compact; daac_scan_count_multi runs its shards on one persistent worker thread + stream per device;
  *                daac_pma_set_option answers 6 for an option that is read at upload once the handle has tables on a device;
  *                gram_version 3 is an alias of 4; the options emit_stagger, emit_v3_lds and the four names of engines that left the
- *                library (restart_tier, emit_tiles, emit_rec_cap, emit_version) are gone. */
+ *                library (restart_tier, emit_tiles, emit_rec_cap, emit_version) are gone.
+ *   (6, additions that change no layout and no enum value: daac_scan_count_batch / daac_scan_batch_device16 — many documents in one call,
+ *      per-document results — and the options batch_piece, batch_lane_max.  A binding that needs them looks the two symbols up.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -299,6 +301,30 @@ typedef struct {
 daac_status daac_scan_count_multi(daac_pma *pma, int mode, int engine, const daac_shard *shards, size_t n, int hay_is_device,
                                   uint64_t *count, uint64_t *checksum);
 
+/* ---- batches: many independent documents in one call --------------------------------------------------------------------------
+ * A batch is one buffer `hay` and n + 1 non-decreasing `offsets`; document i is hay[offsets[i], offsets[i+1]) and the buffer is offsets[n]
+ * bytes long.  Every document gets exactly what the single-haystack call returns on that document alone: a match never crosses a document
+ * boundary, ends (and the checksum's ends) are relative to the document's first byte, ROOT's "" match is reported at each document's 0,
+ * charwise documents are UTF-8 each on their own, and find_iter / leftmost_find_iter start a fresh chain at each document's position 0.
+ * Engines AUTO, TIERED and DARRAY (GRAM and PFX: status 6).  Offsets that decrease are status 1 (device offsets: found by a small
+ * validation kernel, one read-back before the scans); n = 0 is OK.  A leftmost automaton with "" on a document that ends inside a longer
+ * pattern (note D) makes the whole call answer 6, and daac_last_error() names the first such document.  The find_overlapping modes cut
+ * the documents into pieces of option batch_piece bytes, one lane a piece; find_iter / leftmost_find_iter give a document of at most
+ * batch_lane_max bytes one lane and send longer ones through the single-haystack path (about one call's overhead per such document).
+ * Host haystacks are staged in windows of whole documents.  daac_last_kernel() says how the batch was served ("batch pieces=.. lane_docs=..
+ * long_docs=..").
+ *
+ * counts[i] (and checksums[i] when not NULL) for document i = hay[offsets[i], offsets[i+1]).  offsets (n + 1 entries) live where the
+ * haystack lives (hay_is_device); counts / checksums are host arrays, or device arrays when out_is_device != 0, in which case the call is
+ * asynchronous on `stream` after the offsets' validation (find_iter / leftmost_find_iter with long documents synchronise per such document). */
+daac_status daac_scan_count_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                  void *stream, uint64_t *counts, uint64_t *checksums, int out_is_device);
+/* All documents' tuples as one CSR list in device memory: *dev_out holds *total daac_match16 {end, length, value} (end relative to the
+ * document; NULL when there are none), *dev_doc_offsets holds n + 1 u64, and document i's matches are [doc_offsets[i], doc_offsets[i+1]),
+ * in the reference's order.  Both buffers are released with daac_device_free.  The call returns after the stream has finished. */
+daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                     void *stream, daac_match16 **dev_out, uint64_t **dev_doc_offsets, uint64_t *total);
+
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
  * not be resident), byte 0 of the haystack is still `hay`.  For the overlapping modes any `begin` works (charwise:
@@ -405,7 +431,9 @@ void daac_stream_close(daac_stream *s);
  *   pool (1), pool_keep (0)     scratch and result buffers from the device's stream-ordered pool, which keeps up to pool_keep bytes
  *                               between calls (0 = 1/8 of the device memory, at most 32 GiB); read at the first scan of the process
  *   iter_window (64 MiB)        haystack bytes per window of the lazy iterator (the first windows are 16 and 32 MiB: matches arrive early)
- *   max_result_bytes (8 GiB)    largest match list daac_scan may materialise */
+ *   max_result_bytes (8 GiB)    largest match list daac_scan may materialise
+ *   batch_piece (4096)          batches, find_overlapping modes: bytes of a document one lane scans (a piece; entered up to the halo early)
+ *   batch_lane_max (16384)      batches, find_iter / leftmost_find_iter: longest document one lane walks; longer ones take the single-haystack path */
 daac_status daac_set_option(const char *name, int64_t value);
 /* The same option for ONE handle (ABI 5): overrides the process-wide value for every scan, iterator and stream of `pma`, whichever thread runs
  * them (the worker threads of the lazy iterator and of daac_scan_count_multi included).  Two threads scanning two handles with different

@@ -1,4 +1,4 @@
-//! `extern "C"` mirror of include/daachorse_amd.h (ABI version 4).  Plain pointers and sizes only.
+//! `extern "C"` mirror of include/daachorse_amd.h (ABI version 6).  Plain pointers and sizes only.
 #![allow(non_camel_case_types)]
 use core::ffi::{c_char, c_void};
 
@@ -98,6 +98,12 @@ extern "C" {
                             stream: *mut c_void, dev_out: *mut *mut daac_match, count: *mut u64) -> i32;
     pub fn daac_scan_device16(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, len: usize, hay_is_device: i32,
                               stream: *mut c_void, dev_out: *mut *mut daac_match16, count: *mut u64) -> i32;
+    /// many documents in one call: document i = hay[offsets[i], offsets[i+1]); counts / checksums per document
+    pub fn daac_scan_count_batch(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                                 stream: *mut c_void, counts: *mut u64, checksums: *mut u64, out_is_device: i32) -> i32;
+    /// ... and all documents' tuples as one CSR list in device memory (ends relative to the document)
+    pub fn daac_scan_batch_device16(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                                    stream: *mut c_void, dev_out: *mut *mut daac_match16, dev_doc_offsets: *mut *mut u64, total: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
