@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
@@ -17,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "charwise.hpp"
@@ -462,8 +464,20 @@ struct Scratch {
 daac_status upload_locked(daac_pma *pma, int device, DeviceTables **out);   // pma->mu held
 daac_status get_tables(daac_pma *pma, DeviceTables **out);                  // of the current device, uploading on first use
 // api_scan.hip
-struct CountRoute { bool g1_can, g2_can, gw_can, gram, pfx; };   // the GRAM table sets that can serve; GRAM at all; PFX (before its probe of the text)
-CountRoute count_route(const daac_pma *pma, const DeviceTables *t, int mode, int engine, bool want_checksum, uint64_t span);
+// Which kernel family counts a request (count, or count + checksum) and its launch values: what scan_count_impl runs, daac_pma_info's plan reports.
+enum class CountKernel { gram4, gram, gram2, gram2w, pfx, walkers };
+struct CountPlan {
+    CountKernel kernel = CountKernel::walkers;
+    daac_status st = DAAC_OK; const char *err = nullptr;   // refused (`kernel`: the family that refuses) with this error
+    bool probe = false;         // AUTO takes PFX unless the handle's last probe judged the text dense: a new probe may decide
+    bool charwise = false, tier = false;   // walkers: the charwise engine; the TIERED tables
+    Gram4Lds g4{}; uint32_t ppl = 16, threads = 0, lds_bytes = 0;
+    uint64_t region[2] = {16384, 16384};   // default region below / from 2 GiB of scanned bytes
+    uint64_t n_deep = 0, C = 0, K = 0;     // the table set's statistics for `dense`
+    size_t wq_entry = sizeof(uint2);       // walker-queue element
+};
+CountPlan resolve_count(const daac_pma *pma, const DeviceTables *t, int mode, int engine, bool want_checksum, uint64_t span);
+std::pair<int, int> count_ids(const DeviceTables *t, const CountPlan &cp);   // {DAAC_ENGINE_*, DAAC_KERNEL_*}
 daac_status check_mode_kind(const daac_pma *pma, int mode);
 daac_status diverged();
 daac_status make_plan(const daac_pma *pma, const DeviceTables *t, int mode, int engine, uint64_t begin, uint64_t end, Plan &pl, bool &heads);
@@ -480,6 +494,13 @@ daac_status stage_window(const uint8_t *host_hay, uint64_t copy_from, uint64_t e
 hipError_t launch_repack16(const daac_match *in, void *out, unsigned long long n, hipStream_t stream);
 hipError_t launch_repack8(const void *in, void *out, unsigned long long n, unsigned long long base, uint32_t end_bits, hipStream_t stream);
 // api_select.hip
+// The standing part of the emitter's and the selection's gates, which daac_pma_info's plan reports too (the gates add retries and samples).
+constexpr uint32_t kDenseRecPerKib = 26;   // find3 / left3: more deep matches per KiB than this = text of dictionary words
+inline bool emit3_ready(const DeviceTables *t, bool raw) { return (raw ? t->pfx_emit_ok : t->emit3_ok) && OPT(emit) != 0; }
+inline bool emit3_text_ok(const DeviceTables *t) { return t->emit3_gave_up.load() < 2; }
+inline int64_t select_opt(bool leftmost) { return leftmost ? OPT(left3) : OPT(find3); }
+inline bool select_ready(const daac_pma *pma, const DeviceTables *t, bool leftmost) { return (leftmost ? t->left3_ok : t->find3_ok) && select_opt(leftmost) != 0 && !pma->root_has_output(); }
+inline bool select_text_ok(const DeviceTables *t, bool leftmost) { return t->find3_gave_up.load() < 2 && (select_opt(leftmost) >= 2 || t->find3_rec_per_kib.load() <= kDenseRecPerKib + 1); }
 daac_status emit_overlapping3(daac_pma *pma, DeviceTables *t, const uint8_t *dev_hay, uint64_t begin, uint64_t end, hipStream_t stream,
                               DevMatches &out, bool *served, bool raw = false, void *dest = nullptr, uint64_t dest_cap = 0);
 daac_status find_count3(daac_pma *pma, DeviceTables *t, const uint8_t *dev_hay, uint64_t begin, uint64_t len, hipStream_t stream,

@@ -66,6 +66,10 @@ daac_status diverged() {
     return DAAC_ERR_UNSUPPORTED;
 }
 
+static bool on_tier(const daac_pma *pma, const DeviceTables *t, int mode, int engine) {   // the segment scanners' tables: TIERED, else DARRAY
+    return !pma->charwise && mode != DAAC_FIND && mode != DAAC_LEFTMOST_FIND && (engine == DAAC_ENGINE_TIERED || (engine == DAAC_ENGINE_AUTO && t->tier_ok));
+}
+
 daac_status make_plan(const daac_pma *pma, const DeviceTables *t, int mode, int engine, uint64_t begin, uint64_t end, Plan &pl,
                       bool &heads) {
     daac_status kst = check_mode_kind(pma, mode);
@@ -98,7 +102,7 @@ daac_status make_plan(const daac_pma *pma, const DeviceTables *t, int mode, int 
         set_error(engine == DAAC_ENGINE_PFX ? "the PFX engine only serves count (+ checksum) of DAAC_FIND_OVERLAPPING" : "unknown engine");
         return DAAC_ERR_UNSUPPORTED;
     }
-    pl.tier = !pl.charwise && !pl.restart && (engine == DAAC_ENGINE_TIERED || (engine == DAAC_ENGINE_AUTO && t->tier_ok));
+    pl.tier = on_tier(pma, t, mode, engine);
     uint32_t halo = pma->halo();
     // The sync-point scanners decide "is the classic state ROOT here" from a warm-up over the halo, and every lane
     // must reach the same verdict as a lane that has been following the text for longer: Lmax whole bytes, so that a
@@ -135,19 +139,23 @@ daac_status make_plan(const daac_pma *pma, const DeviceTables *t, int mode, int 
     return DAAC_OK;
 }
 
+// count (+ checksum) of an overlapping scan on the walkers: the micro-step walker over segments (2048 lanes per CU, a segment each)
+// instead of the byte-at-a-time segment scanners, where ROOT has no output
+static bool micro_walker(const DeviceTables *t, bool charwise, bool tier) {
+    const int64_t micro = OPT(overlap_micro);
+    return micro != 0 && (charwise || !tier || micro == 2) && (charwise ? t->chr.root_flag : t->da.root_flag) == 0;
+}
+
 hipError_t launch(const DeviceTables *t, const Plan &pl, int kmode, bool heads, hipStream_t s, unsigned long long *next_begin) {
     if (pl.restart && pl.chain.x_prev != nullptr) {  // totals and per-segment counts are sums of tallies; only writing re-scans
         const int pass = kmode == 2 ? 2 : 3;
         return pl.charwise ? launch_char_chain(t->chr, pl.a, pl.chain, pass, kmode, pl.leftmost, next_begin, pl.blocks, s)
                            : launch_chain(t->da, pl.a, pl.chain, pass, kmode, pl.leftmost, next_begin, pl.blocks, s);
     }
-    // count (+ checksum) of an overlapping scan the GRAM tables do not serve: the micro-step walker over segments (2048 lanes
-    // per CU, a segment each) instead of the byte-at-a-time segment scanners
-    if (kmode == 0 && !pl.restart && OPT(overlap_micro) != 0 && (pl.charwise || !pl.tier || OPT(overlap_micro) == 2) &&
+    if (kmode == 0 && !pl.restart && micro_walker(t, pl.charwise, pl.tier) &&
         pl.a.seg_bytes + pl.a.halo < (1ull << 30)) {  // (the walker counts in 32-bit offsets from where it enters its segment)
         const uint32_t blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(t->num_cu) * 8, (pl.a.nseg + 255) / 256)));
-        if (pl.charwise && t->chr.root_flag == 0) return launch_char_overlap_count(t->chr, pl.a, heads, blocks, s);
-        if (!pl.charwise && t->da.root_flag == 0) return launch_overlap_count(t->da, pl.a, heads, blocks, s);
+        return pl.charwise ? launch_char_overlap_count(t->chr, pl.a, heads, blocks, s) : launch_overlap_count(t->da, pl.a, heads, blocks, s);
     }
     if (pl.charwise) {
         return pl.restart ? launch_char_restart_scan(t->chr, pl.a, kmode, pl.leftmost, next_begin, pl.blocks, pl.threads, s)
@@ -370,21 +378,86 @@ daac_status stage_window(const uint8_t *host_hay, uint64_t copy_from, uint64_t e
 }
 
 
-// Which engine counts an overlapping scan of `span` bytes (scan_count_impl runs what this says; fill_plan reports it).  GRAM: the second
-// table set where it applies (count only: always; with the checksum: when CID / H fit next to M), else the first, else the wide one; PFX:
-// what AUTO takes where no GRAM table set applies (before the text has been probed: PFX is a filter, and dense text goes to the walkers).
+// gram4's launch shape (profiles/r05_gram4_decomposition.txt: p32 rfull 1 420, p32 coarse 1 378, p16 rfull 1 326 GB/s): 32 positions per lane first, then
+// the per-word directory (two LDS reads per hit instead of five); eight waves where sixteen do not fit.  gram4_plan gives exactly that shape or nothing.
+static bool gram4_shape(const DeviceTables *t, CountPlan &cp) {
+    const bool want_rfull = OPT(gram2_rfull) != 0, want_arith = OPT(gram4_arith) != 0, want_filter = OPT(gram4_filter) != 0;
+    const uint32_t waves = static_cast<uint32_t>(OPT(threads)) > 512 ? 16u : 8u;
+    const int64_t ppl_opt = OPT(gram_ppl);   // (16 or 32: that shape only)
+    struct Shape { uint32_t ppl; bool rfull; } shapes[4] = {{32u, true}, {32u, false}, {16u, true}, {16u, false}};
+    for (uint32_t w = waves; w >= 8u; w >>= 1)
+        for (const Shape &sh : shapes)
+            if ((sh.ppl == ppl_opt || (ppl_opt != 16 && ppl_opt != 32)) && (want_rfull || !sh.rfull) &&
+                gram4_plan(t->gram4, sh.ppl, w, sh.rfull, want_arith, want_filter, 160u * 1024u, cp.g4)) { cp.ppl = sh.ppl; return true; }
+    return false;
+}
+
+// Which kernel family counts a request of `span` bytes, and how it is launched.  GRAM: the second table set where it applies (`.count()` alone:
+// gram4_kernels.hip on its renumbered tables; with the checksum: when CID / H fit next to M), else the first, else the wide one; PFX: what AUTO
+// takes where no GRAM table set applies, unless the handle's last probe found the text dense (PFX is a filter); otherwise the walkers.
 // (measured on cfg3: with the checksum both table sets spend three LDS lookups per position and the first is a little faster; `.count()`
 // alone needs one lookup per position on the second and runs 20-25 % faster there)
-CountRoute count_route(const daac_pma *pma, const DeviceTables *t, int mode, int engine, bool want_checksum, uint64_t span) {
-    CountRoute r{};
+CountPlan resolve_count(const daac_pma *pma, const DeviceTables *t, int mode, int engine, bool want_checksum, uint64_t span) {
+    CountPlan cp{};
+    auto refuse = [&](const char *err, CountKernel kernel = CountKernel::walkers) { cp.kernel = kernel; cp.st = DAAC_ERR_UNSUPPORTED; cp.err = err; return cp; };
     const int64_t gv = OPT(gram_version);
-    r.g1_can = t->gram_ok && gv != 2;
-    r.g2_can = t->gram2_ok && (!want_checksum || t->gram2.exact_ok) && gv != 1 && !(gv == 0 && want_checksum && r.g1_can);
-    r.gw_can = t->gramw_ok && (!want_checksum || t->gramw.exact_ok);  // wide alphabets: built only where the others are not
+    const bool g1_can = t->gram_ok && gv != 2;
+    const bool g2_can = t->gram2_ok && (!want_checksum || t->gram2.exact_ok) && gv != 1 && !(gv == 0 && want_checksum && g1_can);
+    const bool gw_can = t->gramw_ok && (!want_checksum || t->gramw.exact_ok);  // wide alphabets: built only where the others are not
     const bool applies = !pma->charwise && mode == DAAC_FIND_OVERLAPPING && pma->host.is_standard() && span < (1ull << 35);
-    r.gram = applies && (engine == DAAC_ENGINE_GRAM || (engine == DAAC_ENGINE_AUTO && (r.g2_can || r.g1_can || r.gw_can)));
-    r.pfx = applies && t->pfx_ok && (engine == DAAC_ENGINE_PFX || (engine == DAAC_ENGINE_AUTO && !r.gram));
-    return r;
+    const bool gram = applies && (engine == DAAC_ENGINE_GRAM || (engine == DAAC_ENGINE_AUTO && (g2_can || g1_can || gw_can)));
+    bool pfx = applies && t->pfx_ok && (engine == DAAC_ENGINE_PFX || (engine == DAAC_ENGINE_AUTO && !gram));
+    cp.probe = pfx && engine == DAAC_ENGINE_AUTO && OPT(pfx_probe) != 0;
+    if (cp.probe && t->pfx_dense.load() > 0) pfx = false;   // (no verdict yet: PFX)
+    if (engine == DAAC_ENGINE_PFX && !pfx) return refuse("PFX engine not available for this automaton / request (bytewise Standard automata without \"\", count (+ checksum) of find_overlapping)");
+    if (engine == DAAC_ENGINE_GRAM && !(gram && (g2_can || g1_can || gw_can))) return refuse("GRAM engine not available for this automaton / mode");
+    cp.threads = std::min(1024u, std::max(64u, static_cast<uint32_t>(OPT(threads)) & ~63u));
+    // (second table set and PFX: 256 KiB regions once there are several per wave — a region's start costs a handful of dependent loads and
+    // the refill of the prefetch pipeline: 64 KiB regions measured 2-6 % slower on 4 GiB)
+    if (gram && g2_can) {
+        cp.region[0] = 65536; cp.region[1] = 262144; cp.n_deep = t->gram2.n_deep; cp.C = t->gram2.C; cp.K = t->gram2.K;
+        // (gram_version = 2 asks for gram2_kernels.hip, which counts with its checksum tables: a dictionary without room for those counts on gram4)
+        if (!want_checksum && t->gram4_ok && (gv == 4 || gv == 0 || (gv == 2 && !t->gram2.exact_ok)) && gram4_shape(t, cp)) {
+            cp.kernel = CountKernel::gram4; cp.threads = cp.g4.threads; cp.lds_bytes = cp.g4.lds_bytes; cp.wq_entry = sizeof(uint4);
+            return cp;
+        }
+        if (gv == 4 && !want_checksum)
+            return refuse("gram_version = 4: the gram4 tables are not there for this automaton (or do not fit the LDS with the launch shape asked for)", CountKernel::gram4);
+        // (`.count()` alone lives on gram4_kernels.hip; what is left of gram2_kernels.hip computes the checksum too)
+        if (!t->gram2.exact_ok) return refuse("GRAM second table set: `.count()` runs on the gram4 kernel (gram_version 0 or 4); the count + checksum kernel needs tables this dictionary has no room for", CountKernel::gram2);
+        cp.kernel = CountKernel::gram2; cp.lds_bytes = gram2_lds_bytes(t->gram2, want_checksum);
+    } else if (gram && g1_can) {
+        cp.kernel = CountKernel::gram; cp.lds_bytes = t->gram.lds_bytes; cp.ppl = !t->gram.has_short && OPT(gram_ppl) != 16 ? 32 : 16;
+        cp.n_deep = t->gram.n_deep; cp.C = t->gram.C; cp.K = t->gram.K;
+    } else if (gram) {   // (the wide kernel has one launch shape)
+        cp.kernel = CountKernel::gram2w; cp.threads = 1024; cp.lds_bytes = want_checksum ? t->gramw.lds_exact : t->gramw.lds_count;
+        cp.n_deep = t->gramw.n_deep; cp.C = t->gramw.C; cp.K = 2;
+    } else if (pfx) {
+        cp.kernel = CountKernel::pfx; cp.region[0] = 65536; cp.region[1] = 262144;
+        cp.threads = t->pfx.threads; cp.lds_bytes = t->pfx.lds_bytes; cp.wq_entry = sizeof(uint4);
+    } else {
+        cp.charwise = pma->charwise; cp.tier = on_tier(pma, t, mode, engine);
+    }
+    return cp;
+}
+
+std::pair<int, int> count_ids(const DeviceTables *t, const CountPlan &cp) {
+    switch (cp.kernel) {
+    case CountKernel::gram4: return {DAAC_ENGINE_GRAM, DAAC_KERNEL_GRAM_COUNT};
+    case CountKernel::gram: case CountKernel::gram2: return {DAAC_ENGINE_GRAM, DAAC_KERNEL_GRAM_EXACT};
+    case CountKernel::gram2w: return {DAAC_ENGINE_GRAM, DAAC_KERNEL_GRAM_WIDE};
+    case CountKernel::pfx: return {DAAC_ENGINE_PFX, DAAC_KERNEL_PFX};
+    default: return {cp.tier ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY, micro_walker(t, cp.charwise, cp.tier) ? DAAC_KERNEL_MICRO : DAAC_KERNEL_SEGMENT};
+    }
+}
+
+// what daac_last_kernel() says: the kernel family and, for the `.count()` kernel, the launch shape the options gave it
+static std::string count_kernel_name(const CountPlan &cp) {
+    static const char *const family[] = {"gram4", "gram", "gram2", "gram2w", "pfx"};
+    if (cp.kernel == CountKernel::walkers) return cp.charwise ? "charwise" : cp.tier ? "tiered" : "darray";
+    if (cp.kernel != CountKernel::gram4) return family[static_cast<int>(cp.kernel)];
+    return "gram4 ppl=" + std::to_string(cp.ppl) + " dir=" + std::to_string(cp.g4.dir) + " waves=" + std::to_string(cp.g4.threads / 64) + " arith=" +
+           std::to_string(cp.g4.arith) + " filter=" + std::to_string(cp.g4.filter) + " tail=" + (OPT(gram_tail) < 0 ? std::string("auto") : std::to_string(OPT(gram_tail) > 0 ? 1 : 0));
 }
 
 }  // namespace api
@@ -405,73 +478,25 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
     daac_status st = check_mode_kind(pma, mode);
     if (st != DAAC_OK) return st;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;
-    // which engine and which GRAM table set serve this request (count_route: the decision daac_pma_info's plan reports as well)
-    const int64_t gv = OPT(gram_version);
-    const CountRoute route = count_route(pma, t, mode, engine, want_checksum, len - begin);
-    const bool g1_can = route.g1_can, g2_can = route.g2_can, gw_can = route.gw_can, use_gram = route.gram;
-    bool use_pfx = route.pfx;
-    if (use_pfx && engine == DAAC_ENGINE_AUTO && OPT(pfx_probe) != 0) {
-        // PFX is a filter: where the text's G-grams are mostly trie prefixes the micro-step walker over the double array is faster.  A
-        // synchronous scan of a device haystack of 32 MiB or more samples the text (one small kernel + a read-back) and leaves its
-        // verdict in the handle; every other call goes by the last verdict (none yet: PFX).
-        int dense = t->pfx_dense.load();
-        if (hay_is_device && !result_dev && len - begin >= (32ull << 20) && t->pfx_probe_word) {
-            unsigned int *pin = pinned_words();
-            unsigned int got = 0;
-            unsigned int *tmp = const_cast<unsigned int *>(t->pfx_probe_word);   // (concurrent scans of one handle may read each other's sample: any of them is a sample)
-            HIP_TRY(launch_pfx_probe(t->pfx, hay + begin, len - begin, tmp, stream));
-            HIP_TRY(hipMemcpyAsync(pin ? pin : &got, tmp, 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (pin) got = *pin;
-            dense = got > static_cast<unsigned int>(std::max<int64_t>(0, OPT(pfx_probe))) ? 1 : 0;
-            t->pfx_dense.store(dense);
-        }
-        if (dense > 0) use_pfx = false;   // (no verdict yet: PFX, as the handle's plan says)
+    // which kernel family counts this request and how it is launched (resolve_count: what daac_pma_info's plan reports as well)
+    CountPlan cp = resolve_count(pma, t, mode, engine, want_checksum, len - begin);
+    if (cp.probe && hay_is_device && !result_dev && len - begin >= (32ull << 20) && t->pfx_probe_word) {
+        // A synchronous scan of a device haystack of 32 MiB or more that PFX may serve samples the text (one small kernel + a read-back) and
+        // leaves its verdict in the handle; every other call goes by the last verdict.
+        unsigned int *pin = pinned_words();
+        unsigned int got = 0;
+        unsigned int *tmp = const_cast<unsigned int *>(t->pfx_probe_word);   // (concurrent scans of one handle may read each other's sample: any of them is a sample)
+        HIP_TRY(launch_pfx_probe(t->pfx, hay + begin, len - begin, tmp, stream));
+        HIP_TRY(hipMemcpyAsync(pin ? pin : &got, tmp, 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (pin) got = *pin;
+        t->pfx_dense.store(got > static_cast<unsigned int>(std::max<int64_t>(0, OPT(pfx_probe))) ? 1 : 0);
+        cp = resolve_count(pma, t, mode, engine, want_checksum, len - begin);
     }
-    if (engine == DAAC_ENGINE_PFX && !use_pfx) {
-        set_error("PFX engine not available for this automaton / request (bytewise Standard automata without \"\", count (+ checksum) of find_overlapping)");
-        return DAAC_ERR_UNSUPPORTED;
-    }
-    if (engine == DAAC_ENGINE_GRAM && (!use_gram || !(g2_can || g1_can || gw_can))) {
-        set_error("GRAM engine not available for this automaton / mode");
-        return DAAC_ERR_UNSUPPORTED;
-    }
-    const bool use_g2 = use_gram && g2_can;
-    // `.count()` alone: gram4_kernels.hip on the renumbered tables (gram4.hpp), derived from the second table set
-    Gram4Lds g4l{};
-    uint32_t g4_ppl = 16;
-    // (gram_version = 2 asks for gram2_kernels.hip, which counts with its checksum tables: a dictionary without room for those counts here)
-    bool use_g4 = use_g2 && !want_checksum && t->gram4_ok && (gv == 4 || gv == 0 || (gv == 2 && !t->gram2.exact_ok));
-    if (use_g4) {
-        const bool want_rfull = OPT(gram2_rfull) != 0, want_arith = OPT(gram4_arith) != 0, want_filter = OPT(gram4_filter) != 0;
-        const uint32_t waves = static_cast<uint32_t>(OPT(threads)) > 512 ? 16u : 8u;
-        const int64_t ppl_opt = OPT(gram_ppl);
-        // preference (profiles/r05_gram4_decomposition.txt: p32 rfull 1 420, p32 coarse 1 378, p16 rfull 1 326 GB/s): 32 positions per lane
-        // first, then the per-word directory (two LDS reads per hit instead of five); eight waves leave the tables more room where sixteen
-        // do not fit.  gram4_plan hands back exactly the shape asked for or nothing.
-        struct Shape { uint32_t ppl; bool rfull; } shapes[4] = {{32u, true}, {32u, false}, {16u, true}, {16u, false}};
-        bool planned = false;
-        for (uint32_t w = waves; w >= 8u && !planned; w >>= 1) {
-            for (const Shape &sh : shapes) {
-                if ((ppl_opt == 16 || ppl_opt == 32) && sh.ppl != static_cast<uint32_t>(ppl_opt)) continue;
-                if (sh.rfull && !want_rfull) continue;
-                if (gram4_plan(t->gram4, sh.ppl, w, sh.rfull, want_arith, want_filter, 160u * 1024u, g4l)) { g4_ppl = sh.ppl; planned = true; break; }
-            }
-        }
-        use_g4 = planned;
-    }
-    if (gv == 4 && use_g2 && !want_checksum && !use_g4) {
-        set_error("gram_version = 4: the gram4 tables are not there for this automaton (or do not fit the LDS with the launch shape asked for)");
-        return DAAC_ERR_UNSUPPORTED;
-    }
-    if (use_g2 && !use_g4 && !t->gram2.exact_ok) {   // (`.count()` alone lives on gram4_kernels.hip; what is left of gram2_kernels.hip computes the checksum too)
-        set_error("GRAM second table set: `.count()` runs on the gram4 kernel (gram_version 0 or 4); the count + checksum kernel needs tables this dictionary has no room for");
-        return DAAC_ERR_UNSUPPORTED;
-    }
-    const bool use_gw = use_gram && !g2_can && !g1_can && gw_can;
+    if (cp.st != DAAC_OK) { set_error(cp.err); return cp.st; }
     Plan pl;
     bool heads = false;
-    if ((st = make_plan(pma, t, mode, (use_gram || use_pfx) ? DAAC_ENGINE_AUTO : engine, begin, len, pl, heads)) != DAAC_OK) return st;
+    if ((st = make_plan(pma, t, mode, cp.kernel != CountKernel::walkers ? DAAC_ENGINE_AUTO : engine, begin, len, pl, heads)) != DAAC_OK) return st;
     if (pl.a.nseg == 0 && begin == 0) pl.a.nseg = 1;  // ROOT's list at end = 0
     void *staged = nullptr;
     const uint8_t *dev_hay = hay;
@@ -504,20 +529,10 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
         pl.a.flags = static_cast<unsigned long long *>(flagbuf);
     }
     std::unique_ptr<void, void (*)(void *)> g3(flagbuf, [](void *p) { if (p) (void)hipFree(p); });
-    if (!find3_served) g_last_engine = use_pfx ? DAAC_ENGINE_PFX : use_gram ? DAAC_ENGINE_GRAM : (pl.tier ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY);
-    if (!find3_served) {   // what daac_last_kernel() says: the kernel family and, for the `.count()` kernel, the launch shape the options gave it
-        if (use_g4) {
-            const int64_t tail_opt = OPT(gram_tail);
-            g_last_kernel = "gram4 ppl=" + std::to_string(g4_ppl) + " dir=" + std::to_string(g4l.dir) + " waves=" + std::to_string(g4l.threads / 64) + " arith=" + std::to_string(g4l.arith) +
-                            " filter=" + std::to_string(g4l.filter) + " tail=" + (tail_opt < 0 ? std::string("auto") : std::to_string(tail_opt > 0 ? 1 : 0));
-        } else {
-            g_last_kernel = use_pfx ? "pfx" : use_gw ? "gram2w" : use_g2 ? "gram2" : use_gram ? "gram" : pl.charwise ? "charwise" : pl.tier ? "tiered" : "darray";
-        }
-    } else {
-        g_last_kernel = "find3";
-    }
+    if (!find3_served) g_last_engine = count_ids(t, cp).first;
+    g_last_kernel = find3_served ? "find3" : count_kernel_name(cp);
     if (find3_served) {
-    } else if ((use_gram || use_pfx) && len != begin) {
+    } else if (cp.kernel != CountKernel::walkers && len != begin) {
         // A shard [begin, len): the occurrences with their end in (begin, len] = those of [from, len) scanned as a haystack of its own,
         // from = begin - halo, minus those of [from, begin) scanned as a haystack of its own (what lies wholly inside the halo) — two launches
         // of the same kernel, the second over at most max_pattern_len - 1 bytes into a scratch result, and one fix-up kernel that subtracts
@@ -530,50 +545,40 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
         ga.lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(sub) & 15u);
         ga.hay_al = sub - ga.lead;
         ga.vlen = ga.lead + static_cast<uint64_t>(len - from);
-        // a power of two >= 2 KiB: regions then never straddle a multiple of 4 GiB (the kernel keeps 32-bit positions per epoch)
+        // a power of two from 2 KiB to 1 GiB: regions then never straddle an epoch, the span the kernel keeps 32-bit positions in (gram4: 2 GiB, the others: 4 GiB)
         uint64_t region = 2048;
-        // (second table set: 256 KiB regions once there are several per wave — a region's start costs a handful of dependent
-        // loads and the refill of the prefetch pipeline: 64 KiB regions measured 2-6 % slower on 4 GiB)
-        const int64_t region_opt = OPT(gram_region) > 0 ? OPT(gram_region)
-                                   : (use_g2 || use_pfx) ? ((len - from) >= (1ull << 31) ? 262144 : 65536) : 16384;
+        const int64_t region_opt = OPT(gram_region) > 0 ? OPT(gram_region) : static_cast<int64_t>(cp.region[(len - from) >= (1ull << 31)]);
         while (region * 2 <= static_cast<uint64_t>(std::max<int64_t>(2048, region_opt)) && region < (1ull << 30)) region *= 2;
-        ga.ppl = use_pfx ? 16 : use_g4 ? g4_ppl : (!use_g2 && !use_gw && !t->gram.has_short && OPT(gram_ppl) != 16) ? 32 : 16;
+        assert((region & (region - 1)) == 0 && region <= (1ull << 30));
+        ga.ppl = cp.ppl;
         ga.region_bytes = region;
         ga.nregions = (ga.vlen + region - 1) / region;
         ga.result = d_res;
-        uint32_t threads = static_cast<uint32_t>(OPT(threads));
-        threads = std::min(1024u, std::max(64u, threads & ~63u));
-        if (use_gw) threads = 1024;  // the wide kernel has one launch shape
-        if (use_g4) threads = g4l.threads;
-        if (use_pfx) threads = t->pfx.threads;
-        const uint32_t wpb = threads / 64;
+        const uint32_t threads = cp.threads, wpb = threads / 64;
         uint32_t bpc = static_cast<uint32_t>(OPT(blocks_per_cu));
-        const uint32_t gram_lds = use_pfx ? t->pfx.lds_bytes : use_g4 ? g4l.lds_bytes : use_gw ? (want_checksum ? t->gramw.lds_exact : t->gramw.lds_count)
-                                         : use_g2 ? gram2_lds_bytes(t->gram2, want_checksum) : t->gram.lds_bytes;
-        if (bpc == 0) bpc = std::max(1u, std::min(2048u / threads, (160u * 1024u) / gram_lds));
+        if (bpc == 0) bpc = std::max(1u, std::min(2048u / threads, (160u * 1024u) / cp.lds_bytes));
         const uint32_t blocks = static_cast<uint32_t>(
             std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(t->num_cu) * bpc, (ga.nregions + wpb - 1) / wpb)));
         // room for what one step can queue at worst (64 * ppl + 128 walkers) on top of a useful fill level
         ga.wq_slab = static_cast<uint32_t>(std::max<int64_t>(64 * ga.ppl + 128 + 64, OPT(gram_slab)));  // (a step can queue 64 * ppl walkers)
         // more than ~1 % of the (K+1)-grams are trie prefixes: some lane of the wave hits on nearly every position
-        {
-            const uint64_t n_deep = use_gw ? t->gramw.n_deep : use_g2 ? t->gram2.n_deep : t->gram.n_deep, C = use_gw ? t->gramw.C : use_g2 ? t->gram2.C : t->gram.C,
-                           K = use_gw ? 2 : use_g2 ? t->gram2.K : t->gram.K;
-            ga.dense = OPT(gram_dense) >= 0 ? OPT(gram_dense) != 0 : n_deep * 100 > C * C * C * (K == 3 ? C : 1);
-        }
+        ga.dense = OPT(gram_dense) >= 0 ? OPT(gram_dense) != 0 : cp.n_deep * 100 > cp.C * cp.C * cp.C * (cp.K == 3 ? cp.C : 1);
         // gram4: tail records from the hit record on pay on text made of dictionary words (+20 %) and cost 3-4 % elsewhere; unless
         // the option decides, every workgroup samples the haystack at its start and runs the variant the text calls for
         const int64_t tail_opt = OPT(gram_tail);
         void *wq = nullptr;
-        HIP_TRY(dev_malloc(&wq, static_cast<size_t>(blocks) * wpb * ga.wq_slab * ((use_g4 || use_pfx) ? sizeof(uint4) : sizeof(uint2)), stream));
+        HIP_TRY(dev_malloc(&wq, static_cast<size_t>(blocks) * wpb * ga.wq_slab * cp.wq_entry, stream));
         ga.wq = static_cast<uint2 *>(wq);
         ga.sel_want = tail_opt < 0 ? ((len - begin) >= (1ull << 20) ? 2u : 0u) : tail_opt > 0 ? 1u : 0u;
         auto launch_count = [&](const GramArgs &g, uint32_t nblocks) -> hipError_t {
-            return use_pfx ? launch_pfx_scan(t->pfx, g, want_checksum, nblocks, stream)
-                   : use_g4 ? launch_gram4_scan(t->gram4, g, g4l, nblocks, stream)
-                   : use_gw ? launch_gram2w_scan(t->gramw, g, want_checksum, nblocks, stream)
-                   : use_g2 ? launch_gram2_scan(t->gram2, g, want_checksum, nblocks, threads, stream)
-                            : launch_gram_scan(t->gram, g, nblocks, threads, stream);
+            switch (cp.kernel) {
+            case CountKernel::gram4: return launch_gram4_scan(t->gram4, g, cp.g4, nblocks, stream);
+            case CountKernel::gram: return launch_gram_scan(t->gram, g, nblocks, threads, stream);
+            case CountKernel::gram2: return launch_gram2_scan(t->gram2, g, want_checksum, nblocks, threads, stream);
+            case CountKernel::gram2w: return launch_gram2w_scan(t->gramw, g, want_checksum, nblocks, stream);
+            case CountKernel::pfx: return launch_pfx_scan(t->pfx, g, want_checksum, nblocks, stream);
+            default: return hipErrorInvalidValue;
+            }
         };
         hipError_t le = launch_count(ga, blocks);
         DevBuf halo_res;

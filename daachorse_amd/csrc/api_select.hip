@@ -15,10 +15,10 @@ namespace api {
 daac_status emit_overlapping3(daac_pma *pma, DeviceTables *t, const uint8_t *dev_hay, uint64_t begin, uint64_t end, hipStream_t stream,
                               DevMatches &out, bool *served, bool raw, void *dest, uint64_t dest_cap) {
     *served = false;
-    if (!(raw ? t->pfx_emit_ok : t->emit3_ok) || OPT(emit) == 0 || end <= begin) return DAAC_OK;
+    if (!emit3_ready(t, raw) || end <= begin) return DAAC_OK;
     // (short scans may still try: they cost little; of the large ones every sixteenth looks again — one pair of adversarial haystacks
     // is not the text of a long-lived handle for ever)
-    if (t->emit3_gave_up.load() >= 2 && end - begin >= (1u << 20) && (t->emit3_retry.fetch_add(1) & 15u) != 15u) return DAAC_OK;
+    if (!emit3_text_ok(t) && end - begin >= (1u << 20) && (t->emit3_retry.fetch_add(1) & 15u) != 15u) return DAAC_OK;
     const Gram2EmitDev &e = raw ? t->pfx_emit : t->emit;
     const Gram3Lds &L = t->emit3_lds;
     const uint64_t halo = pma->halo();
@@ -217,15 +217,14 @@ static daac_status find_count3_window(daac_pma *pma, DeviceTables *t, const uint
                                       bool want_checksum, bool leftmost, unsigned long long r[3], uint64_t *next_begin, bool *served,
                                       SelectEmit *em = nullptr) {
     *served = false;
-    const int64_t optv = leftmost ? OPT(left3) : OPT(find3);
+    const int64_t optv = select_opt(leftmost);
     // (DAAC_DEBUG_TIMING=1: the stream is waited for at every lap — kernel times; =2: host time between the laps as the call really runs)
     const char *dbg_env = std::getenv("DAAC_DEBUG_TIMING");
     const bool dbg_sync = dbg_env && dbg_env[0] == '1';
     auto lap = [&](const char *what) { if (dbg_env) { if (dbg_sync) (void)hipStreamSynchronize(stream); dbg_mark(what); } };
-    if (!(leftmost ? t->left3_ok : t->find3_ok) || optv == 0 || len <= begin || len - begin > (1ull << 30)) return DAAC_OK;
+    if (!select_ready(pma, t, leftmost) || len <= begin || len - begin > (1ull << 30)) return DAAC_OK;
     if (t->find3_gave_up.load() >= 2 && len - begin >= (1u << 20) && (t->find3_retry.fetch_add(1) & 15u) != 15u) return DAAC_OK;
     // (option find3 = 2: whatever the text)
-    const uint32_t kDenseRecPerKib = 26;
     if (optv < 2 && t->find3_rec_per_kib.load() > kDenseRecPerKib + 1 && len - begin >= (1u << 20)) {
         // Text of dictionary words goes to the chain walkers without a detection.  Every sixteenth such request looks again — at a SAMPLE:
         // the first 4 MiB go through this function (detection, selection, result thrown away: ~20 us), which refreshes the handle's

@@ -697,55 +697,28 @@ static void fill_plan(const daac_pma *pma, const DeviceTables *t, daac_info &f) 
         f.plan_engine[req] = static_cast<uint8_t>(engine); f.plan_kernel[req] = static_cast<uint8_t>(kernel); f.plan_reason[req] = static_cast<uint8_t>(why);
     };
     for (int r = 0; r < DAAC_REQ_N; ++r) set(r, DAAC_ENGINE_AUTO, DAAC_KERNEL_NONE, t ? DAAC_WHY_FASTEST : DAAC_WHY_NOT_UPLOADED);
-    if (!t) return;
-    if (pma->charwise) {
-        const bool standard = pma->chost.match_kind == DAAC_STANDARD;
-        if (standard) {
-            set(DAAC_REQ_OVERLAPPING_COUNT, DAAC_ENGINE_DARRAY, DAAC_KERNEL_MICRO, DAAC_WHY_CHARWISE);
-            set(DAAC_REQ_OVERLAPPING_CHECKSUM, DAAC_ENGINE_DARRAY, DAAC_KERNEL_MICRO, DAAC_WHY_CHARWISE);
-            set(DAAC_REQ_OVERLAPPING_TUPLES, DAAC_ENGINE_DARRAY, DAAC_KERNEL_SEGMENT, DAAC_WHY_CHARWISE);
-            set(DAAC_REQ_NO_SUFFIX, DAAC_ENGINE_DARRAY, DAAC_KERNEL_SEGMENT, DAAC_WHY_CHARWISE);
-            set(DAAC_REQ_FIND, DAAC_ENGINE_DARRAY, DAAC_KERNEL_CHAIN, DAAC_WHY_CHAIN);
-        } else {
-            set(DAAC_REQ_LEFTMOST_FIND, DAAC_ENGINE_DARRAY, DAAC_KERNEL_CHAIN, DAAC_WHY_CHAIN);
-        }
-        return;
-    }
-    const HostPma &h = pma->host;
-    // find3 / left3 serve the restart iterators' count while the handle's last such request did not meet text made of dictionary words
-    const bool select_text_ok = t->find3_gave_up.load() < 2 && t->find3_rec_per_kib.load() <= 27;
-    if (!h.is_standard()) {
-        if (t->left3_ok && OPT(left3) != 0 && !pma->root_has_output() && (select_text_ok || OPT(left3) >= 2))
-            set(DAAC_REQ_LEFTMOST_FIND, DAAC_ENGINE_GRAM, DAAC_KERNEL_SELECT, DAAC_WHY_FASTEST);
-        else set(DAAC_REQ_LEFTMOST_FIND, DAAC_ENGINE_DARRAY, pma->root_has_output() ? DAAC_KERNEL_SEGMENT : DAAC_KERNEL_CHAIN, DAAC_WHY_CHAIN);
-        return;
-    }
+    if (!t) return;   // (a charwise handle has no table set beside its double array)
+    const bool standard = pma->is_standard();
+    // the restart iterator of the handle's kind: find3 / left3, else the chain walkers over the double array (bytewise, "" in the set: the sync-point scanners)
+    const int find_req = standard ? DAAC_REQ_FIND : DAAC_REQ_LEFTMOST_FIND;
+    if (select_ready(pma, t, !standard) && select_text_ok(t, !standard)) set(find_req, DAAC_ENGINE_GRAM, DAAC_KERNEL_SELECT, DAAC_WHY_FASTEST);
+    else set(find_req, DAAC_ENGINE_DARRAY, !pma->charwise && pma->root_has_output() ? DAAC_KERNEL_SEGMENT : DAAC_KERNEL_CHAIN, DAAC_WHY_CHAIN);
+    if (!standard) return;
     // why the byte-class tables were declined, as far as it is known
-    int why_no_gram = DAAC_WHY_TRIE_SHAPE;
-    if (pma->root_has_output()) why_no_gram = DAAC_WHY_EMPTY_PATTERN;
-    else if (t->n_distinct_bytes > 61) why_no_gram = DAAC_WHY_ALPHABET;
-    else if (t->n_distinct_bytes != 0) why_no_gram = DAAC_WHY_LDS;
-    const int seg_engine = t->tier_ok ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY;
-    const int micro = OPT(overlap_micro) >= (t->tier_ok ? 2 : 1) ? DAAC_KERNEL_MICRO : DAAC_KERNEL_SEGMENT;
-    const int micro_engine = micro == DAAC_KERNEL_MICRO ? DAAC_ENGINE_DARRAY : seg_engine;
-    // count / count + checksum: what scan_count_impl will run (the same decision function)
+    const int why_no_gram = pma->charwise ? DAAC_WHY_CHARWISE : pma->root_has_output() ? DAAC_WHY_EMPTY_PATTERN
+                            : t->n_distinct_bytes > 61 ? DAAC_WHY_ALPHABET : t->n_distinct_bytes != 0 ? DAAC_WHY_LDS : DAAC_WHY_TRIE_SHAPE;
+    // count / count + checksum: what scan_count_impl will run (the same resolver)
     for (const bool cs : {false, true}) {
-        const int req = cs ? DAAC_REQ_OVERLAPPING_CHECKSUM : DAAC_REQ_OVERLAPPING_COUNT;
-        const CountRoute cr = count_route(pma, t, DAAC_FIND_OVERLAPPING, DAAC_ENGINE_AUTO, cs, 0);
-        const int why = (cs && (t->gram2_ok || t->gramw_ok)) ? DAAC_WHY_LDS : why_no_gram;   // (tables there, their checksum half without room)
-        if (cr.gram) set(req, DAAC_ENGINE_GRAM, cr.g2_can ? (cs ? DAAC_KERNEL_GRAM_EXACT : DAAC_KERNEL_GRAM_COUNT) : cr.g1_can ? DAAC_KERNEL_GRAM_EXACT : DAAC_KERNEL_GRAM_WIDE, DAAC_WHY_FASTEST);
-        else if (cr.pfx) set(req, DAAC_ENGINE_PFX, DAAC_KERNEL_PFX, why);
-        else set(req, micro_engine, micro, why);
+        const CountPlan cp = resolve_count(pma, t, DAAC_FIND_OVERLAPPING, DAAC_ENGINE_AUTO, cs, 0);
+        const std::pair<int, int> ids = count_ids(t, cp);   // (GRAM tables there, their checksum half without room: LDS)
+        set(cs ? DAAC_REQ_OVERLAPPING_CHECKSUM : DAAC_REQ_OVERLAPPING_COUNT, ids.first, ids.second,
+            ids.first == DAAC_ENGINE_GRAM ? DAAC_WHY_FASTEST : (cs && (t->gram2_ok || t->gramw_ok)) ? DAAC_WHY_LDS : why_no_gram);
     }
-    if (t->emit3_ok && t->emit3_gave_up.load() < 2 && OPT(emit) != 0)
-        set(DAAC_REQ_OVERLAPPING_TUPLES, DAAC_ENGINE_GRAM, DAAC_KERNEL_GRAM_EMIT, DAAC_WHY_FASTEST);
-    else if (t->pfx_emit_ok && t->emit3_gave_up.load() < 2 && OPT(emit) != 0)
-        set(DAAC_REQ_OVERLAPPING_TUPLES, DAAC_ENGINE_PFX, DAAC_KERNEL_PFX, why_no_gram);
+    const int seg_engine = t->tier_ok ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY;
+    if (emit3_ready(t, false) && emit3_text_ok(t)) set(DAAC_REQ_OVERLAPPING_TUPLES, DAAC_ENGINE_GRAM, DAAC_KERNEL_GRAM_EMIT, DAAC_WHY_FASTEST);
+    else if (emit3_ready(t, true) && emit3_text_ok(t)) set(DAAC_REQ_OVERLAPPING_TUPLES, DAAC_ENGINE_PFX, DAAC_KERNEL_PFX, why_no_gram);
     else set(DAAC_REQ_OVERLAPPING_TUPLES, seg_engine, DAAC_KERNEL_SEGMENT, t->gram2_ok ? DAAC_WHY_DUPLICATES : why_no_gram);
-    set(DAAC_REQ_NO_SUFFIX, seg_engine, DAAC_KERNEL_SEGMENT, DAAC_WHY_FASTEST);
-    if (t->find3_ok && OPT(find3) != 0 && !pma->root_has_output() && (select_text_ok || OPT(find3) >= 2))
-        set(DAAC_REQ_FIND, DAAC_ENGINE_GRAM, DAAC_KERNEL_SELECT, DAAC_WHY_FASTEST);
-    else set(DAAC_REQ_FIND, DAAC_ENGINE_DARRAY, pma->root_has_output() ? DAAC_KERNEL_SEGMENT : DAAC_KERNEL_CHAIN, DAAC_WHY_CHAIN);  // (the restart iterators run on the double array)
+    set(DAAC_REQ_NO_SUFFIX, seg_engine, DAAC_KERNEL_SEGMENT, pma->charwise ? DAAC_WHY_CHARWISE : DAAC_WHY_FASTEST);
 }
 
 daac_status daac_pma_info(const daac_pma *pma, daac_info *info) {

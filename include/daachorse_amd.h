@@ -110,7 +110,8 @@ typedef enum {
 typedef enum {
     DAAC_KERNEL_NONE = 0,        /* the request does not apply to this automaton's MatchKind (the crate panics) */
     DAAC_KERNEL_GRAM_COUNT = 1,  /* gram4_kernels.hip: one LDS lookup per byte, lane-local hit masks           (cfg3: 1.4 TB/s) */
-    DAAC_KERNEL_GRAM_EXACT = 2,  /* gram_kernels.hip / gram2_kernels.hip with the checksum                      (cfg3: 1.0 TB/s) */
+    DAAC_KERNEL_GRAM_EXACT = 2,  /* gram_kernels.hip / gram2_kernels.hip with the checksum, or gram2_kernels.hip counting alone where gram4
+                                  * does not serve (gram_version = 2, no gram4 launch shape fits)              (cfg3: 1.0 TB/s) */
     DAAC_KERNEL_GRAM_WIDE = 3,   /* gram2w_kernels.hip: 31 .. 62 byte classes                                   (1.0 / 0.9 TB/s) */
     DAAC_KERNEL_GRAM_EMIT = 4,   /* emit3_kernels.hip (gram2_emit_kernels.hip behind it): tuples in reference order (cfg3: 0.22 TB/s of haystack) */
     DAAC_KERNEL_PFX = 5,         /* pfx_kernels.hip: any byte alphabet; `.count()` 0.6 - 1.3 TB/s on sparse dictionaries, 0.05 - 0.1 on the

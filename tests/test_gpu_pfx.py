@@ -145,11 +145,39 @@ def test_pfx_on_a_vector_of_window_counts():
         assert len(bad) == 0, (name, bad[:8], got[bad[:8]], want[bad[:8]], los[bad[:8]], his[bad[:8]])
 
 
+# daac_last_kernel()'s family -> the DAAC_KERNEL_* the plan names for it (the walkers' name does not tell SEGMENT from MICRO)
+_PLAN_KERNEL = {"gram4": (1,), "gram": (2,), "gram2": (2,), "gram2w": (3,), "pfx": (5,), "darray": (6, 7), "tiered": (6, 7)}
+
+
+def _counts_run_as_planned(p, hay):
+    """`.count()` and count + checksum: the plan read before the scan names the engine that serves it and the kernel family that runs"""
+    info = p.info()
+    for req, call in ((0, p.count), (1, p.scan_count)):
+        call(ScanMode.FindOverlapping, hay)
+        assert da.last_engine() == info.plan_engine[req], (req, da.last_kernel(), p.explain())
+        assert info.plan_kernel[req] in _PLAN_KERNEL[da.last_kernel().split()[0]], (req, da.last_kernel(), p.explain())
+    return info
+
+
 def test_engine_plan_says_what_will_run():
     """daac_info.plan_* / daac_pma_explain: the engine a request gets is known before the scan, and it is the engine that then serves it"""
     import torch
     REQ = {"count": 0, "checksum": 1, "tuples": 2, "find": 3, "leftmost": 4, "nosuffix": 5}
     hay = torch.from_numpy(synth.uniform_haystack(1 << 20, 3, synth.ALPHA_LOWER_SPACE)).cuda()
+    # the count requests on every kernel family, and under the options that move them from one to another
+    cfg3 = orc.OraclePma.build(synth.patterns_cfg3(30000)).serialize()
+    for opts in ({}, {"gram_version": 1}, {"gram_version": 2}, {"gram_version": 4}, {"gram_ppl": 16}, {"gram_ppl": 32}):
+        p, _ = da.DoubleArrayAhoCorasick.deserialize(cfg3)
+        for k, v in opts.items():
+            p.set_option(k, v)
+        info = _counts_run_as_planned(p.upload(), hay)
+        if opts == {"gram_version": 2}:   # (a dictionary with the count + checksum tables: `.count()` on gram2_kernels.hip)
+            assert da.last_kernel() == "gram2" and info.plan_kernel[0] == 2
+    for pats in (synth.patterns_cfg3_wide(30000), synth.patterns_binary256(5000), synth.patterns_binary256(5000) + [b""]):
+        p, _ = da.DoubleArrayAhoCorasick.deserialize(orc.OraclePma.build(pats).serialize())
+        info = _counts_run_as_planned(p.upload(), hay)
+    # ("" in the set: the segment scanners, not the micro-step walker)
+    assert da.last_kernel() == "darray" and list(info.plan_kernel)[:2] == [6, 6] and list(info.plan_engine)[:2] == [int(Engine.DArray)] * 2
     for pats, kind, expect in ((synth.patterns_cfg3(5000), 0, {"count": (Engine.Gram, 1), "checksum": (Engine.Gram, 2), "tuples": (Engine.Gram, 4), "find": (Engine.Gram, 9)}),
                                (synth.patterns_binary256(5000), 0, {"count": (Engine.Pfx, 5), "checksum": (Engine.Pfx, 5)}),
                                (synth.patterns_cfg3(2000) + [b""], 0, {})):
@@ -374,8 +402,10 @@ def test_the_probe_sends_dense_text_to_the_walker():
     dev = torch.empty(n, dtype=torch.uint8, device="cuda")
     synth.device_zipf_text(dev)
     want = p.count(ScanMode.FindOverlapping, dev, engine=Engine.Pfx)
+    assert list(p.info().plan_engine)[:2] == [int(Engine.Pfx)] * 2   # (no verdict yet)
     assert p.count(ScanMode.FindOverlapping, dev) == want
     assert da.last_engine() == int(Engine.DArray)
+    _counts_run_as_planned(p, dev)   # the plan goes by the verdict too
     res = torch.zeros(3, dtype=torch.int64, device="cuda")
     p.count(ScanMode.FindOverlapping, dev, result_dev=res.data_ptr())      # asynchronous: goes by the verdict in the handle
     assert int(res[0].item()) == want and da.last_engine() == int(Engine.DArray)
@@ -383,6 +413,7 @@ def test_the_probe_sends_dense_text_to_the_walker():
     want = p.count(ScanMode.FindOverlapping, dev, engine=Engine.DArray)
     assert p.count(ScanMode.FindOverlapping, dev) == want
     assert da.last_engine() == int(Engine.Pfx)
+    _counts_run_as_planned(p, dev)
     p.set_option("pfx_probe", 0)
     synth.device_zipf_text(dev)
     p.count(ScanMode.FindOverlapping, dev)
