@@ -496,6 +496,13 @@ daac_status upload_locked(daac_pma *pma, int device, DeviceTables **out) {
                     t->left3_ok = t->find3_ok && left3_lds_bytes(t->find3, true) <= 160u * 1024u;
                     t->find3_ok = false;
                 }
+                // EXPAND places every further copy of a duplicate as an extra, all at the position where the pattern ends, and counts
+                // the extras of a position in 4 bits (emit3_kernels.hip:741): a pattern with more further copies than that gives up every
+                // tile it occurs in, so its tuples go to the segment scanners from the start (decided after find3 / left3: find_iter
+                // reports a state's first output alone and never expands the copies)
+                uint32_t max_copies = 0;
+                for (const U32x4 &r : g2.erec) max_copies = std::max(max_copies, r.w >> 24);
+                t->emit3_ok = t->emit3_ok && max_copies <= kEmit3MaxExtrasAtPosition;
             }
         }
     }

@@ -241,6 +241,7 @@ hipError_t launch_gram4_scan(const Gram4Dev &dev, const GramArgs &a, const Gram4
 // stream + bins into tuples — lanes on CONSECUTIVE positions, so that one store instruction fills neighbouring slots.
 constexpr uint32_t kEmit3Tile = 1024;        // positions per tile (one wave-step of EXPAND; half a wave-step of DETECT)
 constexpr uint32_t kEmit3Chunk = 1024;       // records per chunk of the list (a wave owns one open chunk at a time)
+constexpr uint32_t kEmit3MaxExtrasAtPosition = 15;   // extras ending at one position: EXPAND counts them in 4 bits per position
 constexpr uint32_t kEmit3MaxExtras = 64;     // records per tile the per-position length bits cannot carry (as gram2_emit_kernels.hip)
 constexpr uint32_t kEmit3Stage = 960;        // EXPAND: staged tuples per wave and pass (a tile of more tuples takes several passes)
 // EXPAND, per wave: staged tuples + one dump entry per lane | length bits | first slot per lane | flag bytes per lane | extras | counter

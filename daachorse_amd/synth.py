@@ -370,3 +370,128 @@ def device_zipf_text(tensor, seed=SEEDS["cfg5_hay"], offset=0, codepoints=CFG5_C
     _ffi.check(_ffi.lib().daac_synth_zipf_text(tensor.data_ptr(), tensor.numel(), C.c_uint64(seed), cps.ctypes.data, cw.ctypes.data, len(cps),
                                                ascii_256, ascii[0], ascii[1], slot, C.c_uint64(offset), stream))
     return tensor
+
+
+# ------------------------------------------------------------------------- dictionaries at the limits
+# Seeded families for tests/test_gpu_dictionary_limits.py: values over the whole u32 range, patterns at the lengths where the kernels change
+# the width of a field, many copies of one pattern, and charwise automata around the output-count layouts.  Each returns
+# (patterns, values, text); values are never the pattern index.
+SEEDS["limits"] = 0xDAAC0009
+EDGE_VALUES = (0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFE, 0xFFFFFFFF)
+# every packing edge whose length does not depend on the table set's context length K
+LIMIT_LENGTHS = (19, 20, 31, 32, 33, 63, 64, 65, 255, 256, 1023, 1024, 1025, 4097, 65537)
+# cuts a long match should straddle: gram_region, seg_bytes 16 / 64, batch_piece 256, iter / find3 windows of 4 / 8 / 64 KiB
+LIMIT_CUTS = (16, 64, 256, 2048, 4096, 8192, 65536)
+
+
+def full_range_values(n, seed=SEEDS["limits"]):
+    """n distinct u32 values drawn over the whole range, EDGE_VALUES among them (n >= 6), no value equal to its index"""
+    rng = np.random.default_rng(seed)
+    edges = np.array(EDGE_VALUES[:n], dtype=np.uint64)
+    vals = edges
+    while len(vals) < n:
+        draw = rng.integers(0, 1 << 32, size=n - len(vals) + 64, dtype=np.uint64)
+        draw = np.unique(draw[~np.isin(draw, vals)])
+        vals = np.concatenate([vals, rng.permutation(draw)[:n - len(vals)]])
+    vals = vals[rng.permutation(n)]
+    for i in np.nonzero(vals == np.arange(n, dtype=np.uint64))[0].tolist():
+        j = (i + 1) % n   # swap with a neighbour: the values are distinct, so neither then sits on its own index
+        vals[i], vals[j] = vals[j], vals[i]
+    assert n < 2 or not np.any(vals == np.arange(n, dtype=np.uint64))
+    return vals.astype(np.uint32)
+
+
+def _letters(rng, n, alphabet=ALPHA_LOWER):
+    al = np.frombuffer(bytes(alphabet), dtype=np.uint8)
+    return al[rng.integers(0, len(al), size=n)].tobytes()
+
+
+def _plant(rng, pieces, filler, cuts=LIMIT_CUTS):
+    """filler bytes with every piece placed once, in order, each across a multiple of one of `cuts` (never over another piece)"""
+    out, at = bytearray(), 0
+    for w in pieces:
+        c = int(rng.choice(cuts))
+        start = len(out) + int(rng.integers(0, 300))
+        cut = (start // c + 1) * c
+        start = max(start, cut - int(rng.integers(1, max(2, len(w)))))
+        while len(out) < start:
+            take = min(start - len(out), len(filler) - at)
+            out += filler[at:at + take]
+            at = (at + take) % len(filler)
+        out += w
+    out += filler[at:at + int(rng.integers(0, 500))]
+    return bytes(out)
+
+
+def patterns_values(n=3000, seed=SEEDS["limits"], text_bytes=1 << 20):
+    """cfg3 words with full-range values; a word-soup text of them"""
+    pats = patterns_cfg3(n)
+    return pats, full_range_values(n, seed), wordsoup_haystack(text_bytes, seed, pats, 20, noise_256=40).tobytes()
+
+
+def patterns_lengths(K, seed=SEEDS["limits"], max_len=None, n_words=400, copies=3):
+    """cfg3 words, one random lower-case pattern of every length in {K, K+1, K+16, K+17} + LIMIT_LENGTHS (up to `max_len`), proper prefixes and
+    suffixes of the long ones (long matches nest with short ones), full-range values.  The text is word soup with every long pattern planted
+    `copies` times, each across a region / segment / piece / window cut."""
+    rng = np.random.default_rng(seed)
+    words = patterns_cfg3(n_words)
+    lengths = sorted({K, K + 1, K + 16, K + 17, *LIMIT_LENGTHS})
+    if max_len is not None:
+        lengths = [L for L in lengths if L <= max_len]
+    longs = [_letters(rng, L) for L in lengths]
+    nested = []
+    for w in longs:
+        if len(w) > K + 1:
+            cut = int(rng.integers(K + 1, len(w)))
+            nested += [w[:cut], w[len(w) - cut:], w[:K + 1], w[-(K + 1):]]
+    pats = list(dict.fromkeys(words + longs + nested))   # (distinct: copies are patterns_copies' business)
+    filler = wordsoup_haystack(1 << 18, seed, words, 20, noise_256=40).tobytes()
+    pieces = [longs[int(i)] for i in rng.permutation(np.repeat(np.arange(len(longs)), copies))]
+    return pats, full_range_values(len(pats), seed), _plant(rng, pieces, filler)
+
+
+def patterns_single_long(L, seed=SEEDS["limits"]):
+    """one pattern of L bytes and a text holding it once (the emitter's 2^22 gates)"""
+    rng = np.random.default_rng(seed + L)
+    w = _letters(rng, L)
+    return [w], np.array([0xFFFFFFFF], dtype=np.uint32), _letters(rng, 3000) + w + _letters(rng, 5000)
+
+
+def patterns_copies(n_copies, K, seed=SEEDS["limits"], text_bytes=1 << 16, spacing=None):
+    """one pattern longer than K + 1 bytes registered `n_copies` times, one of K bytes registered twice, a few words; every copy has its own
+    full-range value.  The text is dense: the long pattern every few dozen bytes, or (`spacing`) once every `spacing` bytes between dense
+    stretches of the words, the short pattern and prefixes of the long one"""
+    rng = np.random.default_rng(seed + n_copies)
+    words = patterns_cfg3(200)
+    long_w = _letters(rng, K + 6)
+    short_w = _letters(rng, K)
+    pats = words[:100] + [long_w] * (n_copies // 2) + [short_w, short_w] + words[100:] + [long_w] * (n_copies - n_copies // 2)
+    parts, size = [], 0
+    while size < text_bytes:
+        if spacing is not None and size // spacing != (size + len(long_w)) // spacing:
+            w = long_w   # (ends in the next `spacing` stretch: once per stretch)
+        else:
+            w = (long_w if spacing is None else b" ", short_w, words[int(rng.integers(0, len(words)))],
+                 long_w[:int(rng.integers(1, len(long_w)))])[int(rng.integers(0, 4))]
+        parts.append(w)
+        size += len(w)
+    return pats, full_range_values(len(pats), seed + n_copies), b"".join(parts)[:text_bytes]
+
+
+def patterns_charwise_outputs(n_outputs, seed=SEEDS["limits"], n_words=3000, text_bytes=1 << 18):
+    """a charwise dictionary with exactly `n_outputs` outputs (every pattern adds one, copies included): cfg5 words, then copies of one
+    pattern the text holds at most once (one character outside the text's alphabet); full-range values.  The text is cfg5's Zipf text with
+    the words spliced in"""
+    words = patterns_cfg5(n_words)
+    rare = "一龠".encode("utf-8")   # U+9FA0 lies outside CFG5_CODEPOINTS
+    pats = words + [rare] * (n_outputs - len(words))
+    text = zipf_text(text_bytes, seed)
+    rng = np.random.default_rng(seed)
+    parts, at = [], 0
+    for w in (words[int(i)] for i in rng.integers(0, len(words), size=text_bytes // 64)):
+        step = CFG5_SLOT * int(rng.integers(0, 2))   # (whole slots: cuts on character boundaries)
+        parts += [text[at:at + step].tobytes(), w]
+        at += step
+    body = b"".join(parts)[:text_bytes]
+    body = body[:len(body.decode("utf-8", "ignore").encode("utf-8"))]
+    return pats, full_range_values(len(pats), seed), body + rare

@@ -129,7 +129,7 @@ typedef enum {
     DAAC_WHY_ALPHABET = 2,       /* more distinct pattern bytes than the byte-class tables take (30 / 62) */
     DAAC_WHY_LDS = 3,            /* the tables do not fit the 160 KB of LDS */
     DAAC_WHY_EMPTY_PATTERN = 4,  /* "" is a pattern: every position matches */
-    DAAC_WHY_DUPLICATES = 5,     /* duplicate patterns beyond what the tables encode (more than 3 ending after one context; among patterns of at most K bytes for tuples) */
+    DAAC_WHY_DUPLICATES = 5,     /* duplicate patterns beyond what the tables encode (more than 3 ending after one context; for tuples: among patterns of at most K bytes, or more than 16 copies of one pattern) */
     DAAC_WHY_CHAIN = 6,          /* the iterator is a chain through its own matches: no position-parallel form */
     DAAC_WHY_CHARWISE = 7,       /* a charwise automaton: scanned over its own double array */
     DAAC_WHY_TRIE_SHAPE = 8      /* not a tree-shaped trie / other table limits */

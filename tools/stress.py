@@ -21,6 +21,14 @@ def sev(m):
     return [(int(x["start"]), int(x["end"]), int(x["value"])) for x in m]
 
 
+def random_values(vrng, n):
+    """every other automaton on average: n values drawn over the whole u32 range (else None: value = pattern index).  From a stream of
+    its own, so a seed still draws the same dictionaries, texts and settings it drew before values were added"""
+    if vrng.random() < 0.5:
+        return None
+    return vrng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+
+
 
 
 def iter_soak(budget, seed, max_cases=None):
@@ -103,13 +111,14 @@ def iter_soak(budget, seed, max_cases=None):
 
 
 def gram_soak(seconds, seed, max_cases=None):
-    """count + checksum of the GRAM engine (and TIERED / DARRAY) against the oracle on random dictionaries.
+    """count + checksum of the GRAM engine (and TIERED / DARRAY) against the oracle on random dictionaries, half of them with full-range values.
     `max_cases` set: exactly that many automata whatever the box's speed (the GPU suite); else `seconds`."""
     import torch
     from daachorse_amd import Engine
     rng = np.random.default_rng(seed)
+    vrng = np.random.default_rng(seed ^ 0x5A1E)
     t0 = time.time()
-    n_auto = n_gram = 0
+    n_auto = n_gram = n_vals = 0
     while (n_auto < max_cases) if max_cases is not None else (time.time() - t0 < seconds):
         nsym = int(rng.integers(2, 27))
         syms = rng.choice(np.arange(97, 123), size=nsym, replace=False).astype(np.uint8)
@@ -126,7 +135,9 @@ def gram_soak(seconds, seed, max_cases=None):
             w = np.frombuffer(pats[int(rng.integers(0, npat))], dtype=np.uint8)
             at = int(rng.integers(0, max(1, len(hay) - len(w))))
             hay[at:at + len(w)] = w[:len(hay) - at]
-        o = orc.OraclePma.build(pats)
+        vals = random_values(vrng, len(pats))
+        n_vals += vals is not None
+        o = orc.OraclePma.build(pats, values=vals)
         da_budget = int(rng.choice([158 * 1024, 40 * 1024, 9216]))
         da.set_option("gram_lds_budget", da_budget)
         opts = {"gram_region": int(rng.choice([2048, 16384, 65536])), "gram_slab": int(rng.choice([0, 4096, 20000])),
@@ -161,18 +172,19 @@ def gram_soak(seconds, seed, max_cases=None):
     for k, v in (("gram_lds_budget", 158 * 1024), ("gram_region", 0), ("gram_slab", 4096), ("threads", 1024), ("blocks_per_cu", 0),
                  ("gram_ppl", 0), ("gram_dense", -1), ("seg_bytes", 0), ("gram_version", 0), ("gram2_dpp", 1)):
         da.set_option(k, v)
-    print(f"gram soak ok: {n_auto} automata ({n_gram} on the GRAM engine) in {time.time() - t0:.0f} s (seed {seed})")
+    print(f"gram soak ok: {n_auto} automata ({n_gram} on the GRAM engine, {n_vals} with full-range values) in {time.time() - t0:.0f} s (seed {seed})")
 
 
 def engines_soak(seconds, seed, max_cases=None):
     """The engines of round 3 against the oracle on random dictionaries over random ALPHABETS (2 .. 256 byte values): `.count()` on the gram4
     kernel in every body / launch shape, `.count()` and count + checksum on PFX, and the tuple list of the emitter in both device formats —
-    with duplicate patterns, one-byte patterns and patterns of up to 60 bytes in the mix."""
+    with duplicate patterns, one-byte patterns and patterns of up to 60 bytes in the mix, and full-range values on half the automata."""
     import torch
     from daachorse_amd import Engine
     rng = np.random.default_rng(seed)
+    vrng = np.random.default_rng(seed ^ 0x5A1E)
     t0 = time.time()
-    n_auto = n_g3 = n_pfx = n_emit = n_pfx_emit = 0
+    n_auto = n_g3 = n_pfx = n_emit = n_pfx_emit = n_vals = 0
     da.set_option("pfx", 2)
     while (n_auto < max_cases) if max_cases is not None else (time.time() - t0 < seconds):
         nsym = int(rng.choice([2, 5, 12, 26, 29, 31, 60, 256]))
@@ -194,7 +206,9 @@ def engines_soak(seconds, seed, max_cases=None):
                 hay = np.where(noise, rng.choice(np.array([int(syms.min()) - 1, int(syms.max()) + 1, 0, 255, int(rng.integers(0, 256))]) % 256, size=n), hay).astype(np.uint8)
         else:  # text made of the patterns themselves
             hay = np.frombuffer(b"".join(pats[int(i)] for i in rng.integers(0, len(pats), size=n // max(1, (lo + hi) // 2) + 1))[:n], dtype=np.uint8).copy()
-        o = orc.OraclePma.build(pats)
+        vals = random_values(vrng, len(pats))
+        n_vals += vals is not None
+        o = orc.OraclePma.build(pats, values=vals)
         da.set_option("gram_lds_budget", int(rng.choice([158 * 1024, 40 * 1024])))
         opts = {"gram_region": int(rng.choice([0, 2048, 65536])), "gram_ppl": int(rng.choice([0, 16, 32])), "gram3_tail": int(rng.choice([-1, 0, 1])),
                 "gram_version": int(rng.choice([0, 4])), "gram4_arith": int(rng.choice([1, 1, 0])), "gram2_rfull": int(rng.choice([0, 1])), "threads": int(rng.choice([1024, 512])),
@@ -270,7 +284,7 @@ def engines_soak(seconds, seed, max_cases=None):
     for k, v in (("gram_lds_budget", 158 * 1024), ("gram_region", 0), ("gram_ppl", 0), ("gram3_tail", -1), ("gram4_arith", 1), ("gram4_filter", 1), ("gram_version", 0), ("gram2_rfull", 1), ("threads", 1024),
                  ("pfx", 1)):
         da.set_option(k, v)
-    print(f"engines soak ok: {n_auto} automata ({n_g3} with GRAM tables, {n_pfx} with PFX tables, {n_emit} tuple lists from the GRAM emitter, {n_pfx_emit} from PFX's) in {time.time() - t0:.0f} s (seed {seed})")
+    print(f"engines soak ok: {n_auto} automata ({n_g3} with GRAM tables, {n_pfx} with PFX tables, {n_emit} tuple lists from the GRAM emitter, {n_pfx_emit} from PFX's, {n_vals} with full-range values) in {time.time() - t0:.0f} s (seed {seed})")
 
 
 def select_soak(seconds, seed, max_cases=None):
