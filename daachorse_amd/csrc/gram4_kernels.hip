@@ -32,6 +32,11 @@
 // Dropped: `derive` by two unaligned ds_read_b32 (five VALU fewer a batch, but an unaligned read is 7x slower than the aligned ones,
 // tools/micro/lds_unaligned.hip).  Not done: survivors carrying a packed context index (the class work would move to every hit, 3.65 batches
 // a step, from 1.6 survivor batches) and a finer coarse directory (its LDS comes out of the Bloom array).
+// Round 9: the text fetch of an interior step — the whole step inside its region, none of its bytes among the haystack's first 16 or past its
+// end, decided from the step's 32-bit offset in the region on the scalar unit — is Q loads at scalar base + the lane's offset + 16 q: no per-lane
+// 64-bit position, no fill, no vlen / lead compares (30 VALU a step -> 1).  The first step of a scan and the fetches that reach past a region's or the
+// haystack's end keep load_chunk.  The step loop counts that offset (32-bit) instead of a 64-bit position.  SQ_INSTS_VALU 20.06 -> 19.22 per byte
+// and lane; cfg3 2.637 -> 2.594 ms per 4 GiB, cfg2 1.272 -> 1.159 ms (profiles/r09_gram4_*.txt): the instructions that went were cheaper than the rest.
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -143,6 +148,8 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     auto below = [&](uint32_t k) -> uint32_t { return (1u << k) - 1u; };  // k <= 29
 
     const uint32_t lane = threadIdx.x & 63;
+    const uint32_t lane_off = pin4(lane * (16u * Q));   // this lane's share of a step, from the step's first byte (pinned: it stays a 32-bit
+                                                        // offset beside a scalar base in the load, not a 64-bit add per chunk)
     const uint32_t wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t C4 = C * 4u, CC4 = C * C * 4u;
     const uint32_t ub4 = g.unused_byte * 0x01010101u;
@@ -504,29 +511,49 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             mcarry = __builtin_amdgcn_readfirstlane(lds_u32(x));
         }
 
-        // the chunks of the step at s0; past the region's end only lane 0's first chunk (it feeds the last step's trailer)
-        auto fetch = [&](uint64_t s0, uint4 (&out)[Q]) {
+        // The chunks of the step at rbase + off.  Where the step lies inside the region and no byte of it can be the haystack's first 16 or
+        // lie past its end — decided on `off` alone, 32-bit and wave-uniform: a region is at most 1 GiB — the load is scalar base + the
+        // lane's loop-invariant offset + 16 q as the immediate: no per-lane 64-bit position, no fill, no vlen / lead tests (round 9).  The
+        // others — the first step of a scan, a step that reaches past the region's or the haystack's end — go through load_chunk as before;
+        // past the region's end only lane 0's first chunk (it feeds the last step's trailer).
+        const uint32_t rlen = static_cast<uint32_t>(rend - rbase);
+        const uint32_t fast_lo = rbase < 16u ? SB : 0u;     // (lead < 16: only a chunk below 16 can begin before it)
+        const uint32_t fast_hi = rlen & ~(SB - 1u);         // off < fast_hi: the whole step ends at or before rend <= vlen
+        auto fetch = [&](uint32_t off, uint4 (&out)[Q]) {
+            if (off >= fast_lo && off < fast_hi) {
+                const uint8_t *__restrict__ base = hay + rbase + off;
+                uint32_t voff = lane_off;
+                asm volatile("" : "+v"(voff));   // (taken here: left to itself the compiler hoists hay + rbase + lane_off and adds `off` per lane, 64-bit)
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    const g4_u32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const g4_u32x4_t *>(base + voff + 16u * q));
+                    out[q] = uint4{t.x, t.y, t.z, t.w};
+                }
+                return;
+            }
+            const uint64_t s0 = rbase + off;
 #pragma unroll
             for (int q = 0; q < Q; ++q) out[q] = uint4{ub4, ub4, ub4, ub4};
-            if (s0 < rend) {
+            if (off < rlen) {
 #pragma unroll
                 for (int q = 0; q < Q; ++q) out[q] = load_chunk(s0 + lane * P + 16u * q);
-            } else if (lane == 0 && s0 < rend + SB) {
+            } else if (lane == 0 && off < rlen + SB) {
                 out[0] = load_chunk(s0);
             }
         };
         uint4 pf0[Q], pf1[Q];
-        fetch(rbase, pf0);
-        fetch(rbase + SB, pf1);
+        fetch(0u, pf0);
+        fetch(SB, pf1);
+        const uint32_t rbias = static_cast<uint32_t>(rbase - epoch_base) - (tb + 16u);   // posbias of the region's first step
 
-        for (uint64_t sb = rbase; sb < rend; sb += SB) {
+        for (uint32_t off = 0; off < rlen; off += SB) {
             if (wq_n + 64u * P + 128u + drain_early > a.wq_slab) drain();
             uint4 cur[Q];
 #pragma unroll
             for (int q = 0; q < Q; ++q) { cur[q] = pf0[q]; pf0[q] = pf1[q]; }
             consume_pending();  // before the next chunk is requested: loads retire in order
             __builtin_amdgcn_s_setprio(0);
-            fetch(sb + 2ull * SB, pf1);
+            fetch(off + 2u * SB, pf1);
 
             // ---- what the last step left in the queue leaves the slot; then this step's text goes in ----
             if (q_tail != q_head) {
@@ -537,7 +564,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             q_head = q_tail = 0;
             const uint32_t slot = tb;                             // wave-uniform
             const uint32_t my_text = slot + 16u + lane * P;       // LDS address of this lane's first byte
-            posbias = static_cast<uint32_t>(sb - epoch_base) - (slot + 16u);
+            posbias = rbias + off;
 #pragma unroll
             for (int q = 0; q < Q; ++q)
                 *reinterpret_cast<lds4_u32x4 *>(static_cast<uintptr_t>(my_text + 16u * q)) = g4_u32x4_t{cur[q].x, cur[q].y, cur[q].z, cur[q].w};
