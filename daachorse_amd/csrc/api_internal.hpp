@@ -57,6 +57,7 @@ const char *last_error_cstr();
                                             only, 2 = v2 tables with gram2_kernels.hip, 4 (3: its name until ABI 5) = gram4 or an error */   \
     X(gram4_arith, 1, 0)                 /* gram4: byte classes by arithmetic where the dictionary's bytes are one range (0: class table) */ \
     X(gram4_filter, 1, 0)                /* gram4: the LDS filter in front of rank + gather where it fits (0: per-word rank directory) */      \
+    X(gram4_mph, 8, 1)                   /* gram4: seeds the perfect hash over the depth-(K+1) states may try (gram4_mph.hpp); 0: records by rank */ \
     X(gram2_dpp, 1, 0)                   /* v2: neighbour exchange through DPP wave shifts (0: ds_bpermute) */                               \
     X(find3, 1, 0)                       /* find_iter's count through find3_kernels.hip where the dictionary allows (2: whatever the text,   \
                                             0: the chain walkers always) */                                                                  \

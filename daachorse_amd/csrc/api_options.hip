@@ -29,7 +29,7 @@ daac_status daac_set_option(const char *name, int64_t value) {
 
 // The same option for ONE handle: overrides the process-wide value for every scan, iterator and stream of `pma`.  `unset` != 0 takes the
 // override away.  `pool` / `pool_keep` (the device's allocator) have no per-handle meaning: status 1.  An option that is read when the
-// tables are laid out (gram_lds_budget, lds_budget, pfx, left3, char_map_lds, char_row_lds, dense_depth, rows_share_pct, gram_rank_in_lds)
+// tables are laid out (gram_lds_budget, lds_budget, pfx, left3, char_map_lds, char_row_lds, dense_depth, rows_share_pct, gram_rank_in_lds, gram4_mph)
 // can only be set BEFORE the handle's first upload: afterwards the tables keep their layout, so the call changes nothing and says so
 // (DAAC_ERR_UNSUPPORTED) instead of returning OK for an override that would never take effect (round-5 advisor).
 daac_status daac_pma_set_option(daac_pma *pma, const char *name, int64_t value, int unset) {

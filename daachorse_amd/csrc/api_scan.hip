@@ -457,7 +457,7 @@ static std::string count_kernel_name(const CountPlan &cp) {
     if (cp.kernel == CountKernel::walkers) return cp.charwise ? "charwise" : cp.tier ? "tiered" : "darray";
     if (cp.kernel != CountKernel::gram4) return family[static_cast<int>(cp.kernel)];
     return "gram4 ppl=" + std::to_string(cp.ppl) + " dir=" + std::to_string(cp.g4.dir) + " waves=" + std::to_string(cp.g4.threads / 64) + " arith=" +
-           std::to_string(cp.g4.arith) + " filter=" + std::to_string(cp.g4.filter) + " tail=" + (OPT(gram_tail) < 0 ? std::string("auto") : std::to_string(OPT(gram_tail) > 0 ? 1 : 0));
+           std::to_string(cp.g4.arith) + " filter=" + std::to_string(cp.g4.filter) + " mph=" + std::to_string(cp.g4.mph) + " tail=" + (OPT(gram_tail) < 0 ? std::string("auto") : std::to_string(OPT(gram_tail) > 0 ? 1 : 0));
 }
 
 }  // namespace api

@@ -404,9 +404,18 @@ daac_status upload_locked(daac_pma *pma, int device, DeviceTables **out) {
                 { const U32x4 *x; if ((st = t->put(g4.dhit_t, x)) != DAAC_OK) return st; q.dhit_t = reinterpret_cast<const uint4 *>(x); }
                 { const U32x4 *x; if ((st = t->put(g4.drec_c, x)) != DAAC_OK) return st; q.drec_c = reinterpret_cast<const uint4 *>(x); }
                 { const U32x4 *x; if ((st = t->put(g4.drec_t, x)) != DAAC_OK) return st; q.drec_t = reinterpret_cast<const uint4 *>(x); }
+                // the perfect hash over the depth-(K+1) states (gram4_mph.hpp) first: its displacement table takes the coarse directory's place in the
+                // FILT workgroups' LDS — never more bytes than that — and what it is smaller goes to the Bloom array
+                uint32_t front_bytes = q.s_bytes;
+                if (OPT(gram4_mph) > 0 && build_gram4_mph(g4, q.s_bytes, static_cast<uint32_t>(std::min<int64_t>(OPT(gram4_mph), 64)))) {
+                    if ((st = t->put(g4.mph_disp, q.mph_disp)) != DAAC_OK) return st;
+                    { const U32x2 *x; if ((st = t->put(g4.dhit_h, x)) != DAAC_OK) return st; q.dhit_h = reinterpret_cast<const uint2 *>(x); }
+                    q.mph = g4.mph;
+                    q.mph_bytes = front_bytes = static_cast<uint32_t>(g4.mph_disp.size());
+                }
                 // the filter in front of rank + gather (gram4_filter.hpp): as large as the preferred launch shape leaves room for, less a margin
                 {
-                    const uint32_t room = gram4_filter_room(q.m_bytes, q.s_bytes, g4.arith, 160u * 1024u);
+                    const uint32_t room = gram4_filter_room(q.m_bytes, front_bytes, g4.arith, 160u * 1024u);
                     if (room > 1024u && build_gram4_filter(g4, room - 512u)) {
                         if ((st = t->put(g4.bloom, q.bloom)) != DAAC_OK) return st;
                         q.bloom_words = static_cast<uint32_t>(g4.bloom.size());

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/daachorse_amd.h"
+#include "gram4_mph.hpp"
 
 namespace daac {
 
@@ -212,6 +213,10 @@ struct Gram4Dev {
     const uint4 *drec_t;      // ... from depth K + 2 on
     const uint32_t *bloom;    // the filter in front of rank + gather (gram4_filter.hpp), null when it was not built
     uint32_t bloom_words;     // a multiple of 4
+    const uint8_t *mph_disp;  // the perfect hash over the depth-(K+1) states (gram4_mph.hpp): one displacement per bucket; null when it was not built
+    const uint2 *dhit_h;      // dhit_c's records in the hash's slot order (unused slots zero)
+    G4Mph mph;
+    uint32_t mph_bytes;       // bytes of mph_disp: a multiple of 16, at most s_bytes
     uint32_t m_bytes, rfull_bytes, s_bytes;  // multiples of 16
     uint32_t K, C, s16, arith, lo, unused_byte, n_deep;
 };
@@ -228,9 +233,10 @@ struct Gram4Lds {
     uint32_t filter;       // the workgroups whose text is not made of dictionary words stage [coarse directory | Bloom array] at off_s instead and
     uint32_t off_b;        // ... run the body with the filter: off_b = where the Bloom array then lies, s_bytes_f = bytes of the coarse directory
     uint32_t s_bytes_f;
+    uint32_t mph;          // ... with the perfect hash's displacement table in the coarse directory's place (s_bytes_f = its bytes): records by hash, not by rank
 };
-// the LDS the filter's Bloom array may take at the preferred launch shape (32 positions per lane, 16 waves, coarse directory): what
-// build_gram4_filter is given at upload
+// the LDS the filter's Bloom array may take at the preferred launch shape (32 positions per lane, 16 waves, coarse directory — `sdir_bytes`;
+// the displacement table's bytes in its place where the perfect hash was built): what build_gram4_filter is given at upload
 uint32_t gram4_filter_room(uint32_t m_bytes, uint32_t sdir_bytes, bool arith, uint32_t lds_limit);
 bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, bool want_arith, bool want_filter, uint32_t lds_limit, Gram4Lds &L);
 hipError_t launch_gram4_scan(const Gram4Dev &dev, const GramArgs &a, const Gram4Lds &L, uint32_t blocks, hipStream_t stream);

@@ -45,9 +45,13 @@ DAAC_G4F_HD inline uint32_t g4f_mulhi24(uint32_t a, uint32_t b) {   // v_mul_hi_
     return static_cast<uint32_t>((static_cast<uint64_t>(a & 0xffffffu) * (b & 0xffffffu)) >> 32);
 #endif
 }
+// the 24-bit mix of the K+1 bytes x (first byte lowest) that names the Bloom word — and the bucket of gram4_mph.hpp's perfect hash
+DAAC_G4F_HD inline uint32_t g4f_h(uint32_t x) {
+    return g4f_mad24(x, 0x9E3779u, g4f_mul24(x >> 24, 0x85EBCBu));   // (a further h ^= h >> 15 bought 1 % fewer passes for two instructions: dropped)
+}
 // x = the K+1 bytes p-K .. p (first byte lowest), y = byte p+1; `words` < 2^14
 DAAC_G4F_HD inline G4Probe g4f_probe(uint32_t x, uint32_t y, uint32_t words) {
-    const uint32_t h = g4f_mad24(x, 0x9E3779u, g4f_mul24(x >> 24, 0x85EBCBu));   // (a further h ^= h >> 15 bought 1 % fewer passes for two instructions: dropped)
+    const uint32_t h = g4f_h(x);
     const uint32_t g = g4f_mul24(y, 0x2545F5u) + h;
     G4Probe p;
     // the word: (h mod 2^24) * words / 2^24 in one v_mul_hi_u32_u24 against words << 8 (round 8; before, (h >> 14) * words >> 18 took a

@@ -37,6 +37,10 @@
 // 64-bit position, no fill, no vlen / lead compares (30 VALU a step -> 1).  The first step of a scan and the fetches that reach past a region's or the
 // haystack's end keep load_chunk.  The step loop counts that offset (32-bit) instead of a 64-bit position.  SQ_INSTS_VALU 20.06 -> 19.22 per byte
 // and lane; cfg3 2.637 -> 2.594 ms per 4 GiB, cfg2 1.272 -> 1.159 ms (profiles/r09_gram4_*.txt): the instructions that went were cheaper than the rest.
+// Round 10: a survivor of the filter finds its record by a perfect hash of its K+1 raw bytes (gram4_mph.hpp; MPH below) instead of by its rank: the
+// displacement table (one byte a bucket) lies in LDS where the coarse directory lay, the records in slot order in dhit_h.  10 VALU and one ds_read_u8
+// a batch of 64 survivors instead of 23 and four LDS reads; the TAIL body, the plain body and the density probe keep ranks.  A handle whose dictionary
+// is too dense for a table that small keeps the rank path (build_gram4_mph says no).  profiles/r10_gram4_*.txt.
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -124,10 +128,13 @@ __device__ __forceinline__ void g4_reduce(unsigned long long cnt, unsigned long 
 // from the hit record on and a second pending stage (text made of dictionary words); FILT = a batch of hits goes through the LDS
 // filter of gram4_filter.hpp first and only what passes — collected 64 at a time — is ranked and asks the L2 for its record (round 6;
 // coarse directory, plain records: text made of dictionary words passes the filter anyway and keeps the TAIL body)
-template <int K, int Q, bool ARITH, int DIR, bool TAIL, bool FILT>
+// MPH (FILT only): a survivor's record by the perfect hash of gram4_mph.hpp on its K+1 raw bytes — dhit_h[slot] — instead of dhit_c[rank]; the
+// displacement table lies where the coarse directory would (round 10)
+template <int K, int Q, bool ARITH, int DIR, bool TAIL, bool FILT, bool MPH = false>
 __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a, const Gram4Lds &L, char *smem) {
     static_assert(!(FILT && TAIL), "the filter runs in front of the plain records");
     static_assert(!(FILT && DIR == 0), "the filter's Bloom array lies where the per-word directory would");
+    static_assert(!MPH || FILT, "the perfect hash serves the survivors of the filter");
     constexpr int P = 16 * Q;
     constexpr int GS = 8;
     constexpr uint32_t SB = 64u * P;          // bytes a wave takes per step
@@ -430,11 +437,23 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             pend = uint4{h.x, h.y, 0u, 0u};
         }
     };
-    // FILT, second stage: the n <= 64 survivors in lanes [0, n) of sb_* are ranked and ask for their records
+    // MPH: the record of the hit whose bytes p-3 .. p are x_lo asked for by the hash of its K+1 raw bytes — no class, no M word, no directory:
+    // h and f (2 VALU each: the top byte's product by an SDWA byte select, one v_mad_u32_u24; h is worked out again here rather than carried
+    // from the probe through a fourth ds_permute in every batch of hits, 3.65 a step against 1.6 of these), the bucket and its LDS address (2),
+    // one ds_read_u8, the slot (3), the record's address (1): 10 VALU and 1 LDS read where rank_and_ask takes 23 and 4 (profiles/r10_gram4_isa.txt)
+    const G4Mph mph = g.mph;
+    auto hash_and_ask = [&](uint32_t x_lo) {
+        const uint32_t x = K == 3 ? x_lo : x_lo >> 8;
+        const uint32_t h = g4f_h(x);
+        const uint32_t d = *reinterpret_cast<lds4_cu8 *>(static_cast<uintptr_t>(offS + g4m_bucket(h, mph)));
+        const uint2 r = g.dhit_h[g4m_slot(h, g4m_f(x, mph), d, mph)];
+        pend = uint4{r.x, r.y, 0u, 0u};
+    };
+    // FILT, second stage: the n <= 64 survivors in lanes [0, n) of sb_* are ranked (MPH: hashed) and ask for their records
     auto survivors_ask = [&](uint32_t n) {
         consume_pending();
         pend = uint4{0u, 0u, 0u, 0u};
-        if (lane < n) rank_and_ask(sb_lo);
+        if (lane < n) { if constexpr (MPH) hash_and_ask(sb_lo); else rank_and_ask(sb_lo); }
         fp_pos = sb_pos;
         fp_t0 = lane < n ? sb_t0 : 0u;   // (an idle lane: nothing of it may look like a branch that goes on)
         pend_valid = true;
@@ -681,7 +700,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
 // directory that goes with the choice and runs the body compiled for it (gram3_kernels.hip: two launches with a probe kernel in front
 // cost 60-90 us per scan, a run-time TAIL flag inside one body 10 % of the kernel).  FILT: a workgroup whose text is not made of
 // dictionary words takes [coarse directory | Bloom array] in the place of the per-word directory and runs the body with the filter.
-template <int K, int Q, bool ARITH, int DIR, int TPB, bool FILT>
+template <int K, int Q, bool ARITH, int DIR, int TPB, bool FILT, bool MPH = false>
 __global__ __launch_bounds__(TPB) void gram4_kernel(const Gram4Dev g, const GramArgs a, const Gram4Lds L) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int DIRC = DIR == 0 ? 1 : DIR;   // the coarse directory that goes with the filter (a per-word directory exists only beside u16 entries)
@@ -726,27 +745,32 @@ __global__ __launch_bounds__(TPB) void gram4_kernel(const Gram4Dev g, const Gram
         __syncthreads();
     }
     if (FILT && !tail) {
-        g4_copy(smem + L.off_s, g.sdir, L.s_bytes_f);
+        g4_copy(smem + L.off_s, MPH ? static_cast<const void *>(g.mph_disp) : g.sdir, L.s_bytes_f);
         g4_copy(smem + L.off_b, g.bloom, g.bloom_words * 4u);
     } else {
         g4_copy(smem + L.off_s, DIR == 0 ? static_cast<const void *>(g.rfull) : g.sdir, L.s_bytes);
     }
     __syncthreads();
     if (tail) gram4_body<K, Q, ARITH, DIR, true, false>(g, a, L, smem);
-    else if constexpr (FILT) gram4_body<K, Q, ARITH, DIRC, false, true>(g, a, L, smem);
+    else if constexpr (FILT) gram4_body<K, Q, ARITH, DIRC, false, true, MPH>(g, a, L, smem);
     else gram4_body<K, Q, ARITH, DIR, false, false>(g, a, L, smem);
 }
 
-template <int K, int Q, bool ARITH, int DIR, int TPB, bool FILT>
+template <int K, int Q, bool ARITH, int DIR, int TPB, bool FILT, bool MPH = false>
 static hipError_t launch4_inst(const Gram4Dev &dev, const GramArgs &a, const Gram4Lds &L, uint32_t blocks, hipStream_t stream) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gram4_kernel<K, Q, ARITH, DIR, TPB, FILT>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gram4_kernel<K, Q, ARITH, DIR, TPB, FILT, MPH>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(L.lds_bytes));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram4_kernel<K, Q, ARITH, DIR, TPB, FILT>), dim3(blocks), dim3(TPB), L.lds_bytes, stream, dev, a, L);
+    hipLaunchKernelGGL((gram4_kernel<K, Q, ARITH, DIR, TPB, FILT, MPH>), dim3(blocks), dim3(TPB), L.lds_bytes, stream, dev, a, L);
     return hipGetLastError();
 }
 template <int K, int Q, int TPB, bool ARITH>
 static hipError_t launch4_d(const Gram4Dev &dev, const GramArgs &a, const Gram4Lds &L, uint32_t blocks, hipStream_t stream) {
+    if (L.filter && L.mph) {   // (the FILT body with the hash reads no directory: one instance per TAIL directory the other workgroups may stage)
+        if (L.dir == 0) return launch4_inst<K, Q, ARITH, 0, TPB, true, true>(dev, a, L, blocks, stream);
+        if (L.dir == 1) return launch4_inst<K, Q, ARITH, 1, TPB, true, true>(dev, a, L, blocks, stream);
+        return launch4_inst<K, Q, ARITH, 2, TPB, true, true>(dev, a, L, blocks, stream);
+    }
     if (L.filter) {
         if (L.dir == 0) return launch4_inst<K, Q, ARITH, 0, TPB, true>(dev, a, L, blocks, stream);
         if (L.dir == 1) return launch4_inst<K, Q, ARITH, 1, TPB, true>(dev, a, L, blocks, stream);
@@ -764,7 +788,7 @@ static hipError_t launch4_k(const Gram4Dev &dev, const GramArgs &a, const Gram4L
 // LDS plan of a gram4 launch of `waves` waves per workgroup with `ppl` positions per lane and step:
 // [hit queues | one text slot per wave | class table (256 B, when the classes are not arithmetic) | rank directory | M].
 // `rfull`: the per-word directory (false: one entry per four words).  `want_filter`: the directory's place is made large enough for
-// [coarse directory | Bloom array] as well, for the workgroups that run the body with the filter (gram4_filter.hpp) — not taken when the
+// [coarse directory | Bloom array] — [displacement table of the perfect hash | Bloom array] where the handle has one (gram4_mph.hpp) — as well, for the workgroups that run the body with the filter (gram4_filter.hpp) — not taken when the
 // array was not built or does not fit this shape.  Returns false when the directory asked for is not there or the tables and the
 // per-wave areas do not fit — it never hands back another shape than the one asked for.
 bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, bool want_arith, bool want_filter, uint32_t lds_limit, Gram4Lds &L) {
@@ -782,11 +806,14 @@ bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, b
     L.s_bytes = rfull ? dev.rfull_bytes : dev.s_bytes;
     uint32_t region = L.s_bytes;
     if (want_filter && dev.bloom != nullptr) {
-        const uint32_t with = dev.s_bytes + dev.bloom_words * 4u;
+        // (hash or rank is the upload's decision — the Bloom array was sized for the one it took —: a handle that has the hash runs it)
+        const uint32_t front = dev.mph_disp != nullptr ? dev.mph_bytes : dev.s_bytes;
+        const uint32_t with = front + dev.bloom_words * 4u;
         if (L.off_s + std::max(region, with) + dev.m_bytes <= lds_limit) {
             L.filter = 1u;
-            L.s_bytes_f = dev.s_bytes;
-            L.off_b = L.off_s + dev.s_bytes;
+            L.mph = dev.mph_disp != nullptr ? 1u : 0u;
+            L.s_bytes_f = front;
+            L.off_b = L.off_s + front;
             region = std::max(region, with);
         }
     }

@@ -401,6 +401,9 @@ void daac_stream_close(daac_stream *s);
  *   gram4_filter (1)            the gram4 kernel's LDS filter in front of rank + gather (gram4_filter.hpp, ABI 6): a hit asks the L2 for its record
  *                               only if a Bloom word says the state may end a pattern or go on; workgroups whose text is made of dictionary
  *                               words keep the per-word directory and the tail-record body.  0: round 5's bodies
+ *   gram4_mph (8; read at upload)  a hit that passes that filter finds its record by a perfect hash of its K+1 bytes (gram4_mph.hpp) instead of by its
+ *                               rank: seeds the table builder may try; a dictionary too dense for a displacement table the size of its coarse rank
+ *                               directory keeps the rank path (daac_last_kernel() says mph=0).  0: records by rank
  *   find3 (1)                   find_iter's count (+ checksum) by selection over the tuple emitter's per-position flags (find3_kernels.hip;
  *                               Standard bytewise dictionaries with K = 3 tables and no pattern beyond 19 bytes) instead of the chain walkers,
  *                               in windows of find3_window (2^30) end positions, each restarting at the last match of the one before; a handle
