@@ -93,6 +93,9 @@ int main(int argc, char **argv) {
         std::printf("MISMATCH at tuple %zu of %zu/%zu\n", i, got.size(), want.size());
         return 1;
     }
-    std::printf("OK %lld K=%u C=%u tuples=%zu maxlen=%u\n", n, K, C, got.size(), g.max_len);
+    // deep = the matches of more than K bytes: one record each in the kernels' list (what find3 / left3 weigh per KiB of text)
+    size_t ndeep = 0;
+    for (const auto &d : deep) ndeep += d.size();
+    std::printf("OK %lld K=%u C=%u tuples=%zu deep=%zu maxlen=%u\n", n, K, C, got.size(), ndeep, g.max_len);
     return 0;
 }

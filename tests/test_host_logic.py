@@ -357,6 +357,30 @@ def test_emit_tables_reproduce_the_tuple_stream(tmp_path):
         assert subprocess.check_output([exe, str(blob), "147000", str(h)]).decode().startswith("UNAVAILABLE"), pats
 
 
+def test_cfg3_texts_lie_on_either_side_of_the_dense_gate(tmp_path):
+    """find3 / left3 hand requests of 1 MiB or more to the chain walkers once the last one met more than kDenseRecPerKib = 26 deep matches
+    (longer than K = 3 bytes) per KiB, and remember it as that figure + 1 > 27 (api_select.hip).  The two texts tests/test_gpu_route_memory.py
+    drives that memory with — cfg3's uniform text and its word soup, both generators homogeneous along the text, here their first 2 MiB —
+    counted with the emission tables on the CPU: the uniform text lies below 26 per KiB, the word soup above 27."""
+    exe = str(tmp_path / "emit_check")
+    csrc = os.path.join(ROOT, "daachorse_amd", "csrc")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "native", "emit_check.cpp"),
+                           os.path.join(csrc, "pma.cpp"), os.path.join(csrc, "repack.cpp"), os.path.join(csrc, "gram2.cpp")])
+    pats = synth.patterns_cfg3()
+    blob, h = tmp_path / "a.blob", tmp_path / "h.bin"
+    blob.write_bytes(orc.OraclePma.build(pats).serialize())
+    n = 2 << 20
+    per_kib = {}
+    for name, hay in (("sparse", synth.uniform_haystack(n, synth.SEEDS["cfg3_hay"], synth.ALPHA_LOWER_SPACE)),
+                      ("dense", synth.wordsoup_haystack(n, synth.SEEDS["cfg3_dense"], pats, 20))):
+        hay.tofile(h)
+        out = subprocess.check_output([exe, str(blob), "147000", str(h)]).decode()
+        assert out.startswith("OK") and "K=3" in out, out
+        per_kib[name] = int(out.split("deep=")[1].split()[0]) / (n / 1024)
+    print("deep matches per KiB:", per_kib)
+    assert per_kib["sparse"] < 26 and per_kib["dense"] > 27, per_kib
+
+
 def test_synth_definitions_are_stable():
     """Seeds and generators are part of the benchmark definition: pin a few bytes/patterns."""
     h = synth.uniform_haystack(64, synth.SEEDS["cfg3_hay"], synth.ALPHA_LOWER_SPACE)
