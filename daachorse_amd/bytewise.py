@@ -114,6 +114,8 @@ class _MatchList:
 
 MATCH16_DTYPE = np.dtype([("end", "<u8"), ("length", "<u4"), ("value", "<u4")])  # daac_match16 = the crate's own Match fields
 MATCH8_DTYPE = np.dtype([("value", "<u4"), ("end_len", "<u4")])  # daac_match8: end relative to the run's base | length << end_bits
+OUTPUT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("parent", "<u4")])  # an output record (a pattern's "slot")
+PATTERN_COUNT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("count", "<u8")])
 
 
 class DeviceMatches:
@@ -500,6 +502,40 @@ class DoubleArrayAhoCorasick:
         out["start"] = t16["end"] - t16["length"].astype(np.uint64)
         out["value"] = t16["value"]
         return out, offsets
+
+
+    # ---- histograms: per-pattern match counts of an overlapping scan (daac_pma_outputs / daac_scan_histogram) ---------------------
+    def outputs(self):
+        """-> structured array {value, length, parent} of outputs_len rows: row i is "slot i", the one output record of a pattern
+        (parent: 1-based index of the next record of the output list, 0 = none)"""
+        n = _ffi.lib().daac_pma_outputs(self._h, None, 0)
+        out = np.zeros(n, dtype=OUTPUT_DTYPE)
+        if n:
+            _ffi.lib().daac_pma_outputs(self._h, out.ctypes.data, n)
+        return out
+
+    def histogram(self, mode, haystack, engine=Engine.Auto, stream=None, begin=0, out=None):
+        """-> np.uint64[outputs_len]: counts[i] = matches of slot i's pattern among the matches count(mode, haystack, begin=begin)
+        counts (FindOverlapping / FindOverlappingNoSuffix); with `out` (a CUDA int64 tensor of outputs_len) the counts stay there
+        and the call returns None."""
+        h = _Haystack(haystack)
+        n = _ffi.lib().daac_pma_outputs(self._h, None, 0)
+        if out is not None:
+            _ffi.check(_ffi.lib().daac_scan_histogram(self._h, int(mode), int(engine), h.ptr, h.len, begin, h.is_device, stream,
+                                                      _device_u64(out, n), 1))
+            return None
+        counts = np.zeros(n, dtype=np.uint64)
+        _ffi.check(_ffi.lib().daac_scan_histogram(self._h, int(mode), int(engine), h.ptr, h.len, begin, h.is_device, stream,
+                                                  counts.ctypes.data if n else None, 0))
+        return counts
+
+    def pattern_counts(self, mode, haystack, **kw):
+        """-> structured array {value, length, count}, one row per pattern (slot): outputs() joined with histogram()"""
+        o = self.outputs()
+        res = np.zeros(len(o), dtype=PATTERN_COUNT_DTYPE)
+        res["value"], res["length"] = o["value"], o["length"]
+        res["count"] = self.histogram(mode, haystack, **kw)
+        return res
 
 
 class _Batch:

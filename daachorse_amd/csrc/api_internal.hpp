@@ -81,7 +81,9 @@ const char *last_error_cstr();
     X(char_map_lds, 1, 1)                /* charwise chain scans: the populated stretch of the code mapper in LDS */                         \
     X(char_row_lds, 1, 1)                /* ... and ROOT's row of children beside it */                                                      \
     X(batch_piece, 4096, 0)              /* batches, overlapping modes: bytes of a document per lane-piece */                                \
-    X(batch_lane_max, 16384, 0)          /* batches, chain modes: longest document one lane walks (longer: the single-haystack path) */
+    X(batch_lane_max, 16384, 0)          /* batches, chain modes: longest document one lane walks (longer: the single-haystack path) */ \
+    X(hist_lds_bins, 16384, 0)           /* histograms: the first slots a workgroup counts in LDS (clamped to what 160 KB minus the engine's tables hold);  \
+                                            16384: the winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */
 
 enum OptionId : int {
 #define X(NAME, DEF, UP) OPT_##NAME,

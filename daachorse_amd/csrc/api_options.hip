@@ -18,11 +18,18 @@ found:
     return true;
 }
 
+// values an option cannot take (status 1, as an unknown name)
+static bool option_value_ok(const char *name, int id, int64_t value) {
+    if (id == OPT_hist_lds_bins && value < 0) { set_error(std::string("option ") + name + " counts LDS bins: it cannot be negative"); return false; }
+    return true;
+}
+
 daac_status daac_set_option(const char *name, int64_t value) {
     if (!name) { set_error("null option name"); return DAAC_ERR_INVALID_ARGUMENT; }
     int id = 0;
     bool upload = false;
     if (!option_slot(name, value, id, upload)) { set_error(std::string("unknown option: ") + name); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (!option_value_ok(name, id, value)) return DAAC_ERR_INVALID_ARGUMENT;
     g_opt.v[id].store(value);
     return DAAC_OK;
 }
@@ -37,6 +44,7 @@ daac_status daac_pma_set_option(daac_pma *pma, const char *name, int64_t value, 
     int id = 0;
     bool upload = false;
     if (!option_slot(name, value, id, upload)) { set_error(std::string("unknown option: ") + name); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (!unset && !option_value_ok(name, id, value)) return DAAC_ERR_INVALID_ARGUMENT;
     if (id == OPT_pool || id == OPT_pool_keep) { set_error("pool / pool_keep are properties of the device's allocator, not of a handle"); return DAAC_ERR_INVALID_ARGUMENT; }
     if (upload) {
         std::lock_guard<std::mutex> g(pma->mu);

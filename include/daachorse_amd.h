@@ -40,7 +40,9 @@ extern "C" {
  *                gram_version 3 is an alias of 4; the options emit_stagger, emit_v3_lds and the four names of engines that left the
  *                library (restart_tier, emit_tiles, emit_rec_cap, emit_version) are gone.
  *   (6, additions that change no layout and no enum value: daac_scan_count_batch / daac_scan_batch_device16 — many documents in one call,
- *      per-document results — and the options batch_piece, batch_lane_max.  A binding that needs them looks the two symbols up.) */
+ *      per-document results — and the options batch_piece, batch_lane_max.  A binding that needs them looks the two symbols up.)
+ *   (6, likewise: daac_pma_outputs / daac_scan_histogram — per-pattern match counts of an overlapping scan — and the option
+ *      hist_lds_bins.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -326,6 +328,26 @@ daac_status daac_scan_count_batch(daac_pma *pma, int mode, int engine, const uin
 daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
                                      void *stream, daac_match16 **dev_out, uint64_t **dev_doc_offsets, uint64_t *total);
 
+/* ---- histograms: which patterns occurred, and how often -------------------------------------------------------------------------
+ * Every pattern has exactly one output record {value, length, parent} (src/lib.rs:213-218; parent is 1-based, 0 = none): record i, in
+ * the automaton's order, is "slot i".  daac_pma_outputs copies the n = daac_info.outputs_len records (3 u32 each) to `out`, at most `cap`
+ * of them, and returns n.  Host only, no device. */
+size_t daac_pma_outputs(const daac_pma *pma, uint32_t *out, size_t cap);
+/* counts[i] = number of matches of slot i's pattern among the matches daac_scan_count_range(mode, begin) counts: end in (begin, len],
+ * ROOT's list at end 0 when begin == 0.  The sum over i equals that call's count, so the histograms of the shards of one haystack
+ * simply add.  counts has outputs_len u64 and is overwritten; it is a host array, or a device array when counts_is_device != 0 (then
+ * the call is asynchronous on `stream` for a device haystack).  Patterns that share a value are summed by the caller (the records
+ * carry the value).
+ * Modes: DAAC_FIND_OVERLAPPING (every hit counts its whole output list) and DAAC_FIND_OVERLAPPING_NO_SUFFIX (the head of the list
+ * only); DAAC_FIND / DAAC_LEFTMOST_FIND answer 6.  Engines AUTO, TIERED and DARRAY by the rules of the other scans (GRAM and PFX: 6;
+ * charwise handles: their double array).  A MatchKind mismatch is 5, NULL counts with outputs_len > 0 and begin > len are 1, all before
+ * any device work.  An empty haystack or automaton is OK (ROOT's list at 0 is still counted when begin == 0).
+ * The scan adds 1 at the head slot of every hit (32-bit counters, the first hist_lds_bins slots per workgroup in LDS; ranges of 2^32
+ * bytes and more take several launches), and one small kernel then adds every head's total to the ancestors on its parent chain.
+ * daac_last_kernel() says "hist eng=tier|darray|char lds_bins=N". */
+daac_status daac_scan_histogram(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, size_t begin, int hay_is_device,
+                                void *stream, uint64_t *counts, int counts_is_device);
+
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
  * not be resident), byte 0 of the haystack is still `hay`.  For the overlapping modes any `begin` works (charwise:
@@ -437,7 +459,11 @@ void daac_stream_close(daac_stream *s);
  *   iter_window (64 MiB)        haystack bytes per window of the lazy iterator (the first windows are 16 and 32 MiB: matches arrive early)
  *   max_result_bytes (8 GiB)    largest match list daac_scan may materialise
  *   batch_piece (4096)          batches, find_overlapping modes: bytes of a document one lane scans (a piece; entered up to the halo early)
- *   batch_lane_max (16384)      batches, find_iter / leftmost_find_iter: longest document one lane walks; longer ones take the single-haystack path */
+ *   batch_lane_max (16384)      batches, find_iter / leftmost_find_iter: longest document one lane walks; longer ones take the single-haystack path
+ *   hist_lds_bins (16384)       histograms: the first slots (the shortest patterns: slots are in BFS order of the trie) a workgroup counts in LDS
+ *                               before it flushes them to the global counters; clamped to what 160 KB minus the engine's tables hold; 0 = all
+ *                               hits go to global atomics (13 to 27 times slower on the cfg3 dictionary); negative: status 1.  The default is the
+ *                               winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */
 daac_status daac_set_option(const char *name, int64_t value);
 /* The same option for ONE handle (ABI 5): overrides the process-wide value for every scan, iterator and stream of `pma`, whichever thread runs
  * them (the worker threads of the lazy iterator and of daac_scan_count_multi included).  Two threads scanning two handles with different
