@@ -116,6 +116,7 @@ MATCH16_DTYPE = np.dtype([("end", "<u8"), ("length", "<u4"), ("value", "<u4")]) 
 MATCH8_DTYPE = np.dtype([("value", "<u4"), ("end_len", "<u4")])  # daac_match8: end relative to the run's base | length << end_bits
 OUTPUT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("parent", "<u4")])  # an output record (a pattern's "slot")
 PATTERN_COUNT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("count", "<u8")])
+SLOT_COUNT_DTYPE = np.dtype([("slot", "<u4"), ("count", "<u4")])  # daac_slot_count: a row of a batch's documents x slots matrix
 
 
 class DeviceMatches:
@@ -536,6 +537,26 @@ class DoubleArrayAhoCorasick:
         res["value"], res["length"] = o["value"], o["length"]
         res["count"] = self.histogram(mode, haystack, **kw)
         return res
+
+    # ---- per-document pattern counts of a batch, as a CSR matrix (daac_scan_histogram_batch) ------------------------------------
+    def histogram_batch_device(self, mode, docs, engine=Engine.Auto, stream=None):
+        """-> (DeviceMatches of rows {slot, count} (SLOT_COUNT_DTYPE), DeviceOffsets: n + 1 u64 on the device): document i's rows are
+        [offsets[i], offsets[i+1]), one per slot (row of outputs()) that matched in it, in ascending slot order; all four modes.
+        Both are freed with .free() (or when they are collected)."""
+        b = _Batch(docs)
+        ptr, offs, tot = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_scan_histogram_batch(self._h, int(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream,
+                                                        C.byref(ptr), C.byref(offs), C.byref(tot)))
+        return DeviceMatches(ptr.value, tot.value, SLOT_COUNT_DTYPE), DeviceOffsets(offs.value, b.n + 1)
+
+    def histogram_batch(self, mode, docs, engine=Engine.Auto, stream=None):
+        """-> (SLOT_COUNT_DTYPE array of rows, np.uint64[n + 1] offsets into it)"""
+        dm, do = self.histogram_batch_device(mode, docs, engine, stream)
+        try:
+            return dm.to_numpy(), do.to_numpy()
+        finally:
+            dm.free()
+            do.free()
 
 
 class _Batch:

@@ -1,6 +1,7 @@
 // C ABI (include/daachorse_amd.h), part 6: batches — many independent documents in one call (daac_scan_count_batch,
-// daac_scan_batch_device16).  The kernels are batch_kernels.hip; this file validates, stages host haystacks in windows of whole
-// documents, routes the documents the chain modes cannot give one lane to the single-haystack path, and assembles the results.
+// daac_scan_batch_device16, daac_scan_histogram_batch).  The kernels are batch_kernels.hip and batch_hist_kernels.hip; this file
+// validates, stages host haystacks in windows of whole documents, routes the documents the chain modes cannot give one lane to the
+// single-haystack path, and assembles the results.
 #include "api_internal.hpp"
 #include "batch.hpp"
 
@@ -286,9 +287,197 @@ daac_status for_windows(const uint8_t *hay, const uint64_t *offsets, uint64_t n,
     return DAAC_OK;
 }
 
+// A host batch's CSR result from its windows': fn(window) -> a device list of `elem`-byte entries, its m + 1 offsets and its total.
+// One list: the windows' entries back to back, their offsets shifted by the entries before them.
+template <class F>
+daac_status windows_to_csr(const uint8_t *hay, const uint64_t *offsets, uint64_t n, hipStream_t stream, uint64_t elem, F &&fn, void **list,
+                           unsigned long long **doc_off, uint64_t *total) {
+    std::vector<std::pair<void *, uint64_t>> parts;
+    std::vector<uint64_t> h_doc(n + 1, 0);
+    uint64_t tot = 0;
+    auto free_parts = [&]() { for (auto &p : parts) dev_free(p.first, stream); parts.clear(); };
+    daac_status st = for_windows(hay, offsets, n, stream, [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *h_off, uint64_t i0, uint64_t m) {
+        void *wl = nullptr;
+        unsigned long long *wo = nullptr;
+        uint64_t wt = 0;
+        daac_status s = fn(dh, d_off, h_off, i0, m, &wl, &wo, &wt);
+        if (s != DAAC_OK) return s;
+        parts.emplace_back(wl, wt);
+        std::vector<uint64_t> w(m + 1);
+        hipError_t e = hipMemcpyAsync(w.data(), wo, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        dev_free(wo, stream);
+        if (e != hipSuccess) return hip_fail(e, "batch window offsets");
+        for (uint64_t k = 0; k <= m; ++k) h_doc[i0 + k] = tot + w[k];
+        tot += wt;
+        return DAAC_OK;
+    });
+    if (st != DAAC_OK) { free_parts(); return st; }
+    hipError_t e = dev_malloc(list, std::max<uint64_t>(tot, 1) * elem, stream);
+    if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void **>(doc_off), (n + 1) * sizeof(uint64_t), stream);
+    uint64_t at = 0;
+    for (auto &p : parts) {
+        if (e == hipSuccess && p.second) e = hipMemcpyAsync(static_cast<char *>(*list) + at * elem, p.first, p.second * elem, hipMemcpyDeviceToDevice, stream);
+        at += p.second;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(*doc_off, h_doc.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (h_doc goes out of scope)
+    free_parts();
+    if (e != hipSuccess) { dev_free(*list, stream); dev_free(*doc_off, stream); *list = nullptr; *doc_off = nullptr; return hip_fail(e, "batch list assembly"); }
+    *total = tot;
+    return DAAC_OK;
+}
+
 void report(const BatchPlan &bp, const Route &r) {
     g_last_engine = bp.tier ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY;
     g_last_kernel = "batch pieces=" + std::to_string(r.pieces) + " lane_docs=" + std::to_string(r.lane_docs) + " long_docs=" + std::to_string(r.long_docs);
+}
+
+// ---- per-document pattern counts (daac_scan_histogram_batch) ----
+struct HistRoute { uint64_t pieces = 0, records = 0, wave_docs = 0, group_docs = 0, dense_docs = 0; };
+constexpr uint64_t kHistDocMax = (1ull << 32) - 2;         // longest document: a slot takes one match per position and ROOT's at 0, so a u32 count holds
+constexpr uint64_t kHistDenseScratch = 256ull << 20;       // bytes of counter rows the dense route keeps per launch
+constexpr uint32_t kHistDenseDocs = 1024;                  // ... and documents per launch at most
+
+uint64_t hist_doc_limit(const BatchPlan &bp) { return bp.chain ? std::min(bp.lane_max, kHistDocMax) : kHistDocMax; }
+
+daac_status hist_doc_too_long(const BatchPlan &bp, uint64_t doc, uint64_t len) {
+    if (len > kHistDocMax) {
+        set_error("document " + std::to_string(doc) + " has " + std::to_string(len) + " bytes: a per-document count is 32 bits wide (documents below 2^32 - 1 bytes)");
+    } else {
+        set_error("document " + std::to_string(doc) + " has " + std::to_string(len) + " bytes: find_iter / leftmost_find_iter count a document on one lane, up to option "
+                  "batch_lane_max (" + std::to_string(bp.lane_max) + ") bytes; raise the option for longer ones");
+    }
+    return DAAC_ERR_UNSUPPORTED;
+}
+
+// The rows of documents [0, n) of a device haystack as one CSR list: *rows ({slot, count} of 8 bytes), *doc_off (n + 1 entries,
+// device), *total.  `doc0` is the call's number of the window's first document (for the messages).
+daac_status hist_window(daac_pma *pma, DeviceTables *t, const BatchPlan &bp, const uint8_t *hay, const unsigned long long *d_off, uint64_t n, uint64_t doc0,
+                        hipStream_t stream, void **rows, unsigned long long **doc_off, uint64_t *total, HistRoute &route) {
+    *rows = nullptr;
+    *doc_off = nullptr;
+    *total = 0;
+    DevBuf layout;
+    unsigned long long *flags = nullptr, *first = nullptr;
+    uint64_t npieces = 0;
+    daac_status st = batch_layout(bp, d_off, n, stream, layout, flags, first, npieces);
+    if (st != DAAC_OK) return st;
+    BatchArgs a{};
+    a.hay = hay;
+    a.off = d_off;
+    a.n = n;
+    a.first_piece = first;
+    a.npieces = npieces;
+    a.piece_bytes = bp.piece;
+    a.halo = bp.halo;
+    a.lane_max = bp.lane_max;
+    a.flags = flags;
+    // 1. matches per piece (overlapping) or per document (chain); their exclusive scan places the records
+    const uint64_t units = bp.chain ? n : npieces;
+    DevBuf cnt;
+    HIP_TRY(cnt.alloc((units + 4 + exclusive_scan_scratch(units + 1)) * sizeof(unsigned long long), stream));
+    a.counts = static_cast<unsigned long long *>(cnt.p);
+    unsigned long long *d_total = a.counts + units + 1;
+    HIP_TRY(hipMemsetAsync(a.counts, 0, (units + 2) * sizeof(unsigned long long), stream));
+    const TierDev *tier = bp.tier ? &t->tier : nullptr;
+    const DArrayDev *da = (!bp.tier && !pma->charwise) ? &t->da : nullptr;
+    const CharDev *chr = pma->charwise ? &t->chr : nullptr;
+    if (!bp.chain) HIP_TRY(launch_batch_pieces(tier, da, chr, a, 1, bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
+    else HIP_TRY(launch_batch_chain(da, chr, a, 1, bp.leftmost, static_cast<uint32_t>(t->num_cu), stream));
+    HIP_TRY(launch_exclusive_scan(a.counts, units + 1, d_total, d_total + 3, stream));
+    // 2. records per document -> the document's route; the lengths the counts cannot serve
+    const uint64_t m = n + 1;
+    DevBuf work;   // roff[m] (overlapping modes), rowcnt[m], the rows' total, 3 words of scan scratch head room, cls[4], the two lists, scan scratch
+    HIP_TRY(work.alloc(((bp.chain ? 0 : m) + m + 8 + 2 * n + exclusive_scan_scratch(m)) * sizeof(unsigned long long), stream));
+    unsigned long long *roff = bp.chain ? a.counts : static_cast<unsigned long long *>(work.p);   // (chain: the scan of n + 1 counts is the layout)
+    BatchHistArgs h{};
+    h.roff = roff;
+    h.n = n;
+    h.rowcnt = static_cast<unsigned long long *>(work.p) + (bp.chain ? 0 : m);
+    unsigned long long *d_rows_total = h.rowcnt + m;
+    h.cls = d_rows_total + 4;
+    h.group_list = h.cls + 4;
+    h.dense_list = h.group_list + n;
+    unsigned long long *scan_scratch = h.dense_list + n;
+    h.wave_max = static_cast<uint64_t>(std::min<int64_t>(std::max<int64_t>(0, OPT(batch_hist_wave_max)), kBatchHistWaveCap));
+    h.sort_max = static_cast<uint64_t>(std::min<int64_t>(std::max<int64_t>(0, OPT(batch_hist_sort_max)), kBatchHistGroupCap));
+    HIP_TRY(hipMemsetAsync(h.cls, 0, 2 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(h.cls + 2, 0xff, sizeof(unsigned long long), stream));
+    if (!bp.chain) HIP_TRY(launch_batch_doc_offsets(first, a.counts, n, d_total, roff, stream));
+    HIP_TRY(launch_batch_hist_classify(h, d_off, hist_doc_limit(bp), stream));
+    unsigned long long *pin = reinterpret_cast<unsigned long long *>(pinned_words());
+    unsigned long long local[5];
+    unsigned long long *hw = pin ? pin : local;   // {group docs, dense docs, first too long document, records, first note D document}
+    HIP_TRY(hipMemcpyAsync(hw, h.cls, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(hw + 3, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(hw + 4, flags + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t group_docs = hw[0], dense_docs = hw[1], too_long = hw[2], tot = hw[3], first_d = hw[4];
+    if (too_long != kNone) {
+        unsigned long long ends[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(ends, d_off + too_long, sizeof(ends), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return hist_doc_too_long(bp, doc0 + too_long, ends[1] - ends[0]);
+    }
+    if (bp.leftmost && pma->root_has_output() && first_d != kNone) return note_d(doc0 + first_d);
+    if (tot * 8 > static_cast<unsigned long long>(OPT(max_result_bytes))) {
+        set_error(std::to_string(tot) + " match records of 8 bytes exceed max_result_bytes");
+        return DAAC_ERR_INVALID_AUTOMATON;   // (status 4 is this call's answer; the tuple lists answer 2 for theirs)
+    }
+    // 3. one record per match, then every document's rows at the front of its records
+    DevBuf rec;
+    HIP_TRY(rec.alloc(std::max<uint64_t>(tot, 1) * sizeof(unsigned long long), stream));
+    a.rec = static_cast<unsigned long long *>(rec.p);
+    h.rec = a.rec;
+    if (tot) {
+        if (!bp.chain) HIP_TRY(launch_batch_pieces(tier, da, chr, a, 3, bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
+        else HIP_TRY(launch_batch_chain(da, chr, a, 3, bp.leftmost, static_cast<uint32_t>(t->num_cu), stream));
+    }
+    const uint64_t wave_docs = n - group_docs - dense_docs;
+    if (wave_docs) HIP_TRY(launch_batch_hist_sort(h, true, n, static_cast<uint32_t>(t->num_cu), stream));
+    HIP_TRY(launch_batch_hist_sort(h, false, group_docs, static_cast<uint32_t>(t->num_cu), stream));
+    DevBuf scratch;
+    if (dense_docs) {
+        const uint64_t slots = pma->charwise ? pma->chost.outputs.size() : pma->host.outputs.size();
+        const uint64_t per = std::min<uint64_t>({dense_docs, kHistDenseDocs, std::max<uint64_t>(1, kHistDenseScratch / (4 * std::max<uint64_t>(slots, 1)))});
+        HIP_TRY(scratch.alloc(per * slots * sizeof(uint32_t), stream));
+        for (uint64_t d0 = 0; d0 < dense_docs; d0 += per) {
+            const uint32_t nd = static_cast<uint32_t>(std::min<uint64_t>(per, dense_docs - d0));
+            HIP_TRY(hipMemsetAsync(scratch.p, 0, nd * slots * sizeof(uint32_t), stream));
+            HIP_TRY(launch_batch_hist_dense(h, static_cast<uint32_t *>(scratch.p), slots, d0, nd, stream));
+        }
+    }
+    // 4. rows per document -> the call's offsets, 5. the rows to their place
+    HIP_TRY(launch_exclusive_scan(h.rowcnt, m, d_rows_total, scan_scratch, stream));
+    unsigned long long nrows = 0;
+    HIP_TRY(hipMemcpyAsync(&nrows, d_rows_total, sizeof(nrows), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    void *out = nullptr;
+    unsigned long long *doffs = nullptr;
+    HIP_TRY(dev_malloc(&out, std::max<uint64_t>(nrows, 1) * sizeof(daac_slot_count), stream));
+    std::unique_ptr<void, std::function<void(void *)>> out_guard(out, [stream](void *p) { dev_free(p, stream); });
+    HIP_TRY(dev_malloc(reinterpret_cast<void **>(&doffs), m * sizeof(unsigned long long), stream));
+    std::unique_ptr<void, std::function<void(void *)>> off_guard(doffs, [stream](void *p) { dev_free(p, stream); });
+    HIP_TRY(launch_batch_hist_copy(h.rec, roff, h.rowcnt, n, nrows, static_cast<unsigned long long *>(out), stream));
+    HIP_TRY(hipMemcpyAsync(doffs, h.rowcnt, m * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // (the scratch of this window is freed next)
+    route.pieces += npieces;
+    route.records += tot;
+    route.wave_docs += wave_docs;
+    route.group_docs += group_docs;
+    route.dense_docs += dense_docs;
+    (void)off_guard.release();
+    *rows = out_guard.release();
+    *doc_off = doffs;
+    *total = nrows;
+    return DAAC_OK;
+}
+
+void report_hist(const BatchPlan &bp, const HistRoute &r) {
+    g_last_engine = bp.tier ? DAAC_ENGINE_TIERED : DAAC_ENGINE_DARRAY;
+    g_last_kernel = "batch_hist pieces=" + std::to_string(r.pieces) + " records=" + std::to_string(r.records) + " wave_docs=" + std::to_string(r.wave_docs) +
+                    " group_docs=" + std::to_string(r.group_docs) + " dense_docs=" + std::to_string(r.dense_docs);
 }
 
 }  // namespace
@@ -364,37 +553,11 @@ daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const 
         st = tuples_window(pma, t, bp, mode, engine, hay, reinterpret_cast<const unsigned long long *>(offsets), nullptr, n, stream, &list, &doc_off, &tot, route);
         if (st != DAAC_OK) return st;
     } else {
-        // every window's list, then one list: the windows' tuples back to back, their offsets shifted by the tuples before them
-        std::vector<std::pair<void *, uint64_t>> parts;
-        std::vector<uint64_t> h_doc(n + 1, 0);
-        auto free_parts = [&]() { for (auto &p : parts) dev_free(p.first, stream); parts.clear(); };
-        st = for_windows(hay, offsets, n, stream, [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *h_off, uint64_t i0, uint64_t m) {
-            void *wl = nullptr;
-            unsigned long long *wo = nullptr;
-            uint64_t wt = 0;
-            daac_status s = tuples_window(pma, t, bp, mode, engine, dh, d_off, h_off, m, stream, &wl, &wo, &wt, route);
-            if (s != DAAC_OK) return s;
-            parts.emplace_back(wl, wt);
-            std::vector<uint64_t> w(m + 1);
-            hipError_t e = hipMemcpyAsync(w.data(), wo, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            dev_free(wo, stream);
-            if (e != hipSuccess) return hip_fail(e, "batch window offsets");
-            for (uint64_t k = 0; k <= m; ++k) h_doc[i0 + k] = tot + w[k];
-            tot += wt;
-            return DAAC_OK;
-        });
-        if (st != DAAC_OK) { free_parts(); return st; }
-        hipError_t e = dev_malloc(&list, std::max<uint64_t>(tot, 1) * 16, stream);
-        if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void **>(&doc_off), (n + 1) * sizeof(uint64_t), stream);
-        uint64_t at = 0;
-        for (auto &p : parts) {
-            if (e == hipSuccess && p.second) e = hipMemcpyAsync(static_cast<char *>(list) + at * 16, p.first, p.second * 16, hipMemcpyDeviceToDevice, stream);
-            at += p.second;
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(doc_off, h_doc.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
-        free_parts();
-        if (e != hipSuccess) { dev_free(list, stream); dev_free(doc_off, stream); return hip_fail(e, "batch list assembly"); }
+        st = windows_to_csr(hay, offsets, n, stream, 16, [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *h_off, uint64_t, uint64_t m,
+                                                            void **wl, unsigned long long **wo, uint64_t *wt) {
+            return tuples_window(pma, t, bp, mode, engine, dh, d_off, h_off, m, stream, wl, wo, wt, route);
+        }, &list, &doc_off, &tot);
+        if (st != DAAC_OK) return st;
     }
     HIP_TRY(hipStreamSynchronize(stream));
     if (tot == 0) { dev_free(list, stream); list = nullptr; HIP_TRY(hipStreamSynchronize(stream)); }
@@ -402,6 +565,58 @@ daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const 
     *dev_doc_offsets = reinterpret_cast<uint64_t *>(doc_off);
     *total = tot;
     report(bp, route);
+    return DAAC_OK;
+}
+
+static_assert(sizeof(daac_slot_count) == sizeof(unsigned long long), "a row takes a record's place");
+
+daac_status daac_scan_histogram_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                      void *stream_, daac_slot_count **dev_rows, uint64_t **dev_doc_offsets, uint64_t *total) {
+    PmaScope scope_(pma);
+    daac_status st = batch_precheck(pma, mode, hay, offsets, n, hay_is_device);
+    if (st != DAAC_OK) return st;
+    if (!dev_rows || !dev_doc_offsets || !total) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_rows = nullptr;
+    *dev_doc_offsets = nullptr;
+    *total = 0;
+    BatchPlan bp;
+    if ((st = batch_engine(pma, nullptr, mode, engine, bp)) != DAAC_OK) return st;
+    if (n && !hay_is_device) {   // the lengths the counts cannot serve, before a device is touched
+        const uint64_t limit = hist_doc_limit(bp);
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] - offsets[i] > limit) return hist_doc_too_long(bp, i, offsets[i + 1] - offsets[i]);
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) {   // one offset, 0
+        void *z = nullptr;
+        HIP_TRY(hipMalloc(&z, sizeof(uint64_t)));
+        HIP_TRY(hipMemset(z, 0, sizeof(uint64_t)));
+        *dev_doc_offsets = static_cast<uint64_t *>(z);
+        report_hist(bp, HistRoute{});
+        return DAAC_OK;
+    }
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;
+    if ((st = batch_engine(pma, t, mode, engine, bp)) != DAAC_OK) return st;
+    HistRoute route;
+    void *rows = nullptr;
+    unsigned long long *doc_off = nullptr;
+    uint64_t tot = 0;
+    if (hay_is_device) {
+        st = hist_window(pma, t, bp, hay, reinterpret_cast<const unsigned long long *>(offsets), n, 0, stream, &rows, &doc_off, &tot, route);
+    } else {
+        st = windows_to_csr(hay, offsets, n, stream, sizeof(daac_slot_count), [&](const uint8_t *dh, const unsigned long long *d_off, const uint64_t *, uint64_t i0,
+                                                                                 uint64_t m, void **wl, unsigned long long **wo, uint64_t *wt) {
+            return hist_window(pma, t, bp, dh, d_off, m, i0, stream, wl, wo, wt, route);
+        }, &rows, &doc_off, &tot);
+    }
+    if (st != DAAC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (tot == 0) { dev_free(rows, stream); rows = nullptr; HIP_TRY(hipStreamSynchronize(stream)); }
+    *dev_rows = static_cast<daac_slot_count *>(rows);
+    *dev_doc_offsets = reinterpret_cast<uint64_t *>(doc_off);
+    *total = tot;
+    report_hist(bp, route);
     return DAAC_OK;
 }
 

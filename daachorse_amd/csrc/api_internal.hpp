@@ -83,7 +83,10 @@ const char *last_error_cstr();
     X(batch_piece, 4096, 0)              /* batches, overlapping modes: bytes of a document per lane-piece */                                \
     X(batch_lane_max, 16384, 0)          /* batches, chain modes: longest document one lane walks (longer: the single-haystack path) */ \
     X(hist_lds_bins, 16384, 0)           /* histograms: the first slots a workgroup counts in LDS (clamped to what 160 KB minus the engine's tables hold);  \
-                                            16384: the winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */
+                                            16384: the winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */ \
+    X(batch_hist_wave_max, 2048, 0)      /* batch histograms: most records of a document that one wave sorts in LDS (at most 4096) */            \
+    X(batch_hist_sort_max, 16384, 0)     /* ... and that one workgroup sorts (at most 32768: what 160 KB hold); above: dense counters in HBM;    \
+                                            both from tools/time_batch_hist.py's sweep (profiles/r12_batch_hist_time.json) */
 
 enum OptionId : int {
 #define X(NAME, DEF, UP) OPT_##NAME,

@@ -21,6 +21,10 @@ found:
 // values an option cannot take (status 1, as an unknown name)
 static bool option_value_ok(const char *name, int id, int64_t value) {
     if (id == OPT_hist_lds_bins && value < 0) { set_error(std::string("option ") + name + " counts LDS bins: it cannot be negative"); return false; }
+    if ((id == OPT_batch_hist_wave_max || id == OPT_batch_hist_sort_max) && value < 0) {
+        set_error(std::string("option ") + name + " counts a document's records: it cannot be negative");
+        return false;
+    }
     return true;
 }
 

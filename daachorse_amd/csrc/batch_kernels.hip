@@ -9,7 +9,7 @@
 // start) bytes early at ROOT — the segment scanners' argument (scan_kernels.hip), with the document start as a hard floor.  The
 // engines are those of the segment scanners (scan_engines.hpp).  MODE 0 leaves {count, S1, S2} per piece (ends relative to the
 // document) and batch_reduce_kernel adds up each document's contiguous piece range; MODE 1 / 2 are the count -> exclusive scan
-// -> write passes, writing daac_match16.
+// -> write passes, writing daac_match16; MODE 3 is the write pass of daac_scan_histogram_batch: one 8-byte slot record per match.
 //
 // Chain modes (find_iter, leftmost_find_iter): one lane walks one whole document with ChainWalker (chain_scan.hpp) from its
 // position 0 to its end; with "" in the set, find_iter reports every position and leftmost_find_iter runs the sync-point
@@ -94,12 +94,14 @@ __global__ __launch_bounds__(1024) void batch_piece_kernel(const typename Eng::D
         unsigned long long cnt = 0;
         uint32_t s1 = 0, s2 = 0, e = 0;  // e = end - lo of the byte just consumed
         uint4 *o = nullptr;
+        unsigned long long *o8 = nullptr;
         if (MODE == 2) o = a.out + a.counts[j];
+        if (MODE == 3) o8 = a.rec + a.counts[j];
 
         typename Eng::State st = eng.root();
 
         auto emit = [&](const typename Eng::State &s) {
-            if (MODE != 2) {
+            if (MODE < 2) {
                 if (HEADS) {  // FindOverlappingNoSuffixIterator: only the head of the list
                     const uint32_t *r = eng.outputs() + 3u * (eng.opos(s) - 1u);
                     const uint32_t h = match_hash32_dev(r[0], r[1]);
@@ -108,6 +110,13 @@ __global__ __launch_bounds__(1024) void batch_piece_kernel(const typename Eng::D
                     const uint2 q = eng.sum(s);
                     cnt += q.x; s1 += q.y; s2 += q.y * e;
                 }
+            } else if (MODE == 3) {  // the slot of every record of the list (HEADS: of its head)
+                uint32_t op = eng.opos(s);
+                do {
+                    const uint32_t slot = op - 1u;
+                    op = HEADS ? 0u : eng.outputs()[3u * slot + 2u];
+                    *o8++ = slot;
+                } while (op != 0);
             } else {
                 uint32_t op = eng.opos(s);
                 const uint64_t end = rel + e;
@@ -215,7 +224,8 @@ __device__ __attribute__((noinline)) bool leftmost_empty_doc(const T &t, uint64_
     }
 }
 
-// KMODE 0: {count, S1, S2} per document into res; 1: count per document; 2: write at out + counts[doc].
+// KMODE 0: {count, S1, S2} per document into res; 1: count per document; 2: write at out + counts[doc]; 3: slot records at
+// rec + counts[doc].
 // walk(h, len, emit) scans the document at h and returns false on note D.
 template <int KMODE, class Walk>
 __device__ __forceinline__ void batch_docs_body(const BatchArgs &a, const uint32_t *outputs, Walk &&walk) {
@@ -226,11 +236,15 @@ __device__ __forceinline__ void batch_docs_body(const BatchArgs &a, const uint32
         unsigned long long cnt = 0;
         uint32_t s1 = 0, s2 = 0;
         uint4 *o = nullptr;
+        unsigned long long *o8 = nullptr;
         if (KMODE == 2) o = a.out + a.counts[i];
+        if (KMODE == 3) o8 = a.rec + a.counts[i];
         auto emit = [&](uint32_t opos, uint64_t end) {
             const uint32_t *r = outputs + 3u * (opos - 1u);
             const uint32_t value = r[0], length = r[1];
-            if (KMODE == 2) {
+            if (KMODE == 3) {
+                o8[cnt] = opos - 1u;
+            } else if (KMODE == 2) {
                 o[cnt] = uint4{static_cast<uint32_t>(end), static_cast<uint32_t>(end >> 32), length, value};
             } else {
                 const uint32_t h = match_hash32_dev(value, length);
@@ -328,7 +342,8 @@ static hipError_t launch_pieces_eng(const typename Eng::Dev &dev, const BatchArg
     } while (0)
     if (mode == 0) { if (heads) DAAC_BP(0, true); else DAAC_BP(0, false); }
     else if (mode == 1) { if (heads) DAAC_BP(1, true); else DAAC_BP(1, false); }
-    else { if (heads) DAAC_BP(2, true); else DAAC_BP(2, false); }
+    else if (mode == 2) { if (heads) DAAC_BP(2, true); else DAAC_BP(2, false); }
+    else { if (heads) DAAC_BP(3, true); else DAAC_BP(3, false); }
 #undef DAAC_BP
     return hipGetLastError();
 }
@@ -352,12 +367,12 @@ hipError_t launch_batch_chain(const DArrayDev *da, const CharDev *chr, const Bat
 #define DAAC_BC(K, L, M) hipLaunchKernelGGL((K<L, M>), g, b, 0, stream, *dev, a)
     if (da) {
         const DArrayDev *dev = da;
-        if (leftmost) { if (kmode == 0) DAAC_BC(batch_chain_kernel, true, 0); else if (kmode == 1) DAAC_BC(batch_chain_kernel, true, 1); else DAAC_BC(batch_chain_kernel, true, 2); }
-        else { if (kmode == 0) DAAC_BC(batch_chain_kernel, false, 0); else if (kmode == 1) DAAC_BC(batch_chain_kernel, false, 1); else DAAC_BC(batch_chain_kernel, false, 2); }
+        if (leftmost) { if (kmode == 0) DAAC_BC(batch_chain_kernel, true, 0); else if (kmode == 1) DAAC_BC(batch_chain_kernel, true, 1); else if (kmode == 2) DAAC_BC(batch_chain_kernel, true, 2); else DAAC_BC(batch_chain_kernel, true, 3); }
+        else { if (kmode == 0) DAAC_BC(batch_chain_kernel, false, 0); else if (kmode == 1) DAAC_BC(batch_chain_kernel, false, 1); else if (kmode == 2) DAAC_BC(batch_chain_kernel, false, 2); else DAAC_BC(batch_chain_kernel, false, 3); }
     } else {
         const CharDev *dev = chr;
-        if (leftmost) { if (kmode == 0) DAAC_BC(batch_char_chain_kernel, true, 0); else if (kmode == 1) DAAC_BC(batch_char_chain_kernel, true, 1); else DAAC_BC(batch_char_chain_kernel, true, 2); }
-        else { if (kmode == 0) DAAC_BC(batch_char_chain_kernel, false, 0); else if (kmode == 1) DAAC_BC(batch_char_chain_kernel, false, 1); else DAAC_BC(batch_char_chain_kernel, false, 2); }
+        if (leftmost) { if (kmode == 0) DAAC_BC(batch_char_chain_kernel, true, 0); else if (kmode == 1) DAAC_BC(batch_char_chain_kernel, true, 1); else if (kmode == 2) DAAC_BC(batch_char_chain_kernel, true, 2); else DAAC_BC(batch_char_chain_kernel, true, 3); }
+        else { if (kmode == 0) DAAC_BC(batch_char_chain_kernel, false, 0); else if (kmode == 1) DAAC_BC(batch_char_chain_kernel, false, 1); else if (kmode == 2) DAAC_BC(batch_char_chain_kernel, false, 2); else DAAC_BC(batch_char_chain_kernel, false, 3); }
     }
 #undef DAAC_BC
     return hipGetLastError();

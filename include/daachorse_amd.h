@@ -42,7 +42,9 @@ extern "C" {
  *   (6, additions that change no layout and no enum value: daac_scan_count_batch / daac_scan_batch_device16 — many documents in one call,
  *      per-document results — and the options batch_piece, batch_lane_max.  A binding that needs them looks the two symbols up.)
  *   (6, likewise: daac_pma_outputs / daac_scan_histogram — per-pattern match counts of an overlapping scan — and the option
- *      hist_lds_bins.) */
+ *      hist_lds_bins.)
+ *   (6, likewise: daac_slot_count / daac_scan_histogram_batch — per-document pattern counts of a batch, as a CSR matrix — and the
+ *      options batch_hist_wave_max, batch_hist_sort_max.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -348,6 +350,35 @@ size_t daac_pma_outputs(const daac_pma *pma, uint32_t *out, size_t cap);
 daac_status daac_scan_histogram(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, size_t begin, int hay_is_device,
                                 void *stream, uint64_t *counts, int counts_is_device);
 
+/* ---- per-document pattern counts of a batch: which patterns occurred in which document, and how often ----------------------------
+ * The matrix documents x slots in CSR form, in device memory: *dev_rows holds *total rows {slot, count} (NULL when there are none),
+ * *dev_doc_offsets holds n + 1 u64, and document i's rows are [doc_offsets[i], doc_offsets[i+1]): one row per slot (index into
+ * daac_pma_outputs) with a non-zero count in that document, in ascending slot order.  count = the matches of that slot's pattern among
+ * the matches the single-haystack iterator of `mode` reports on the document alone (the contract of daac_scan_count_batch: nothing
+ * crosses a document boundary, ROOT's "" match is reported at each document's 0), so a document's counts add up to its
+ * daac_scan_count_batch count.  The output is a function of the input alone and compares bit for bit between calls.  Both buffers are
+ * released with daac_device_free; the call returns after the stream has finished.  n = 0: *dev_rows = NULL, *dev_doc_offsets = one 0.
+ * The batch arguments are those of daac_scan_batch_device16.  Modes: all four (DAAC_FIND_OVERLAPPING counts the whole output list of
+ * every hit).  Engines and their refusals are the batches': AUTO, TIERED, DARRAY; GRAM / PFX, charwise + TIERED, find_iter /
+ * leftmost_find_iter + TIERED: 6; a MatchKind mismatch: 5.  NULL out-pointers, NULL offsets with n > 0 and offsets that decrease: 1.
+ * A document of 2^32 - 1 bytes or more: 6, naming the document (a slot takes at most one match per position plus ROOT's at 0, so a
+ * 32-bit count cannot wrap below that length).  DAAC_FIND / DAAC_LEFTMOST_FIND with a document longer than option batch_lane_max: 6,
+ * naming the first such document and the option — the single-haystack route the tuple batches give such documents yields
+ * (value, length), not slots; a caller raises batch_lane_max (up to its clamp, 2^30 - 1) and pays one lane's walk over the document.
+ * With host offsets all of these are decided before a device is touched.  Note D (see above): 6, naming the document.  Status 4 when
+ * 8 bytes times the number of matches exceeds max_result_bytes, before the records are allocated (the tuple lists answer 2 there).
+ * Method: one 8-byte record (the slot) per match at the place an exclusive scan of the per-piece / per-document counts gives it, then
+ * a reduction of each document's records by their number R — R <= batch_hist_wave_max: one wave sorts the slots in LDS and run-length
+ * encodes them; R <= batch_hist_sort_max: one workgroup does; above: a row of outputs_len u32 counters in HBM, compacted in slot order
+ * — an exclusive scan of the row counts and a copy.  daac_last_kernel() says "batch_hist pieces=.. records=.. wave_docs=..
+ * group_docs=.. dense_docs=..". */
+typedef struct daac_slot_count {
+    uint32_t slot;        /* index into daac_pma_outputs */
+    uint32_t count;
+} daac_slot_count;
+daac_status daac_scan_histogram_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                      void *stream, daac_slot_count **dev_rows, uint64_t **dev_doc_offsets, uint64_t *total);
+
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
  * not be resident), byte 0 of the haystack is still `hay`.  For the overlapping modes any `begin` works (charwise:
@@ -460,6 +491,10 @@ void daac_stream_close(daac_stream *s);
  *   max_result_bytes (8 GiB)    largest match list daac_scan may materialise
  *   batch_piece (4096)          batches, find_overlapping modes: bytes of a document one lane scans (a piece; entered up to the halo early)
  *   batch_lane_max (16384)      batches, find_iter / leftmost_find_iter: longest document one lane walks; longer ones take the single-haystack path
+ *   batch_hist_wave_max (2048)  per-document pattern counts: most match records of a document that one wave sorts in LDS (clamped to 4096)
+ *   batch_hist_sort_max (16384) ... and that one workgroup sorts (clamped to 32768, what 160 KB of LDS hold); documents with more take a row
+ *                               of outputs_len counters in HBM.  Neither is read at upload; negative values are status 1.  The defaults are
+ *                               the winners of tools/time_batch_hist.py's sweep (profiles/r12_batch_hist_time.json)
  *   hist_lds_bins (16384)       histograms: the first slots (the shortest patterns: slots are in BFS order of the trie) a workgroup counts in LDS
  *                               before it flushes them to the global counters; clamped to what 160 KB minus the engine's tables hold; 0 = all
  *                               hits go to global atomics (13 to 27 times slower on the cfg3 dictionary); negative: status 1.  The default is the
