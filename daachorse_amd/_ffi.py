@@ -120,6 +120,10 @@ def lib():
     L.daac_scan_histogram.restype = C.c_int
     L.daac_scan_histogram_batch.argtypes = [vp, C.c_int, C.c_int, u8p, vp, sz, C.c_int, vp, P(vp), P(vp), P(C.c_uint64)]
     L.daac_scan_histogram_batch.restype = C.c_int
+    L.daac_replace_all.argtypes = [vp, C.c_int, C.c_int, u8p, sz, C.c_int, vp, vp, vp, sz, P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_replace_all.restype = C.c_int
+    L.daac_replace_all_batch.argtypes = [vp, C.c_int, C.c_int, u8p, vp, sz, C.c_int, vp, vp, vp, sz, P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_replace_all_batch.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

@@ -558,6 +558,63 @@ class DoubleArrayAhoCorasick:
             dm.free()
             do.free()
 
+    # ---- replace_all: the text with every match of find_iter / leftmost_find_iter replaced (daac_replace_all[_batch]) ---------------
+    # `replacements`: one bytes / str for every match, or a sequence indexed by the match's value (automata built without values:
+    # the pattern's index).  mode=None: Find for Standard handles, LeftmostFind otherwise.
+    def _replace_mode(self, mode):
+        if mode is not None:
+            return int(mode)
+        return int(ScanMode.Find if self.match_kind() == MatchKind.Standard else ScanMode.LeftmostFind)
+
+    def replace_all(self, haystack, replacements, mode=None, engine=Engine.Auto, stream=None, device=False):
+        """-> bytes; device=True: DeviceMatches of uint8 (to_numpy / free), the result left in device memory"""
+        r = _Replacements(replacements)
+        h = _Haystack(haystack)
+        ptr, n, k = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_replace_all(self._h, self._replace_mode(mode), int(engine), h.ptr, h.len, h.is_device, stream,
+                                               r.blob_ptr, r.off_ptr, r.n, C.byref(ptr), C.byref(n), C.byref(k)))
+        dm = DeviceMatches(ptr.value, n.value, np.dtype(np.uint8))
+        dm.n_replaced = k.value
+        if device:
+            return dm
+        try:
+            return dm.to_numpy().tobytes()
+        finally:
+            dm.free()
+
+    def replace_all_batch(self, docs, replacements, mode=None, engine=Engine.Auto, stream=None, device=False):
+        """-> list of bytes, one per document (each replaced as a haystack of its own); device=True: (DeviceMatches of uint8,
+        DeviceOffsets of n + 1 u64): document i's result is [offsets[i], offsets[i+1])"""
+        r = _Replacements(replacements)
+        b = _Batch(docs)
+        ptr, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_replace_all_batch(self._h, self._replace_mode(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream,
+                                                     r.blob_ptr, r.off_ptr, r.n, C.byref(ptr), C.byref(offs), C.byref(n), C.byref(k)))
+        dm, do = DeviceMatches(ptr.value, n.value, np.dtype(np.uint8)), DeviceOffsets(offs.value, b.n + 1)
+        dm.n_replaced = k.value
+        if device:
+            return dm, do
+        try:
+            out, o = dm.to_numpy().tobytes(), do.to_numpy()
+        finally:
+            dm.free()
+            do.free()
+        return [out[int(o[i]):int(o[i + 1])] for i in range(b.n)]
+
+
+class _Replacements:
+    """The replacements argument as daac_replace_all takes it: one blob + n + 1 offsets (host)."""
+
+    def __init__(self, replacements):
+        parts = [_as_bytes(replacements)] if isinstance(replacements, (str, bytes, bytearray, memoryview)) else [_as_bytes(x) for x in replacements]
+        self.n = len(parts)
+        self.offsets = np.zeros(self.n + 1, dtype=np.uint64)
+        if parts:
+            self.offsets[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        self.blob = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8)
+        self.blob_ptr = self.blob.ctypes.data
+        self.off_ptr = self.offsets.ctypes.data
+
 
 class _Batch:
     """A batch argument: a sequence of documents (str / bytes / uint8 arrays), packed into one host buffer + n + 1 offsets, or a pair

@@ -44,7 +44,9 @@ extern "C" {
  *   (6, likewise: daac_pma_outputs / daac_scan_histogram — per-pattern match counts of an overlapping scan — and the option
  *      hist_lds_bins.)
  *   (6, likewise: daac_slot_count / daac_scan_histogram_batch — per-document pattern counts of a batch, as a CSR matrix — and the
- *      options batch_hist_wave_max, batch_hist_sort_max.) */
+ *      options batch_hist_wave_max, batch_hist_sort_max.)
+ *   (6, likewise: daac_replace_all / daac_replace_all_batch — the text with every match of find_iter / leftmost_find_iter replaced,
+ *      spliced on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -378,6 +380,41 @@ typedef struct daac_slot_count {
 } daac_slot_count;
 daac_status daac_scan_histogram_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
                                       void *stream, daac_slot_count **dev_rows, uint64_t **dev_doc_offsets, uint64_t *total);
+
+/* ---- replace_all: the text with every match replaced ------------------------------------------------------------------------------
+ * With m_0 .. m_{k-1} the matches the iterator of `mode` reports on hay, in its order, and r(m) the replacement of match m, the result is
+ *     hay[0 : start_0] + r(m_0) + hay[end_0 : start_1] + r(m_1) + ... + r(m_{k-1}) + hay[end_{k-1} : len]
+ * (replace_all of the aho-corasick crate over find_iter / leftmost_find_iter).  Modes: DAAC_FIND on Standard automata, DAAC_LEFTMOST_FIND
+ * on the leftmost kinds (a mismatch: 5), bytewise and charwise; positions are bytes.  DAAC_FIND_OVERLAPPING and
+ * DAAC_FIND_OVERLAPPING_NO_SUFFIX: 6 — overlapping matches have no splice.  An empty match ("" among the patterns) is an insertion.
+ * Replacements: n_repl byte strings, replacement i = repl[repl_offsets[i], repl_offsets[i+1]) (host arrays, n_repl + 1 non-decreasing
+ * offsets below 4 GiB; copied to the device on the stream per call).  n_repl == 1: every match takes replacement 0.  Otherwise a match
+ * takes replacement number `value` — automata built without values number them by pattern index, so this is "replacement i for pattern
+ * i"; with values, one replacement per category — and a match whose value is >= n_repl makes the call answer 1 (daac_last_error() names
+ * the value and the match's start; nothing has been allocated for the caller then).  Replacements may be empty (deletion).
+ * The result stays in device memory: *dev_out holds *out_len bytes (NULL when *out_len == 0), released with daac_device_free and copied
+ * with daac_device_to_host; *n_replaced = k.  The call returns after the stream has finished.
+ * Statuses decided before a device is touched: NULL out-pointers, n_repl == 0, repl_offsets NULL or decreasing, repl NULL with a
+ * non-empty blob: 1; the overlapping modes: 6; a MatchKind mismatch: 5.  The tuple list is daac_scan_device16's (the batch:
+ * daac_scan_batch_device16's): its engines and their refusals, note D (6) and the max_result_bytes rule of the list are this call's; a
+ * result longer than max_result_bytes answers 2 before it is allocated.
+ * A host haystack is staged to the device ONCE and whole — the splice reads the text there — not in windows: it has to fit next to the
+ * tuple list and the result.
+ * Method: one lane per match sizes it (replacement length, match length), two exclusive sums give O_i = start_i - sum of the lengths
+ * before + sum of the replacement lengths before, the output position of match i's replacement; after one read-back of the totals the
+ * result is allocated and written output-parallel, 16 bytes a lane: output byte q belongs to the largest i with O_i <= q (replacement
+ * byte q - O_i, or the text behind end_i), which is what makes matches that share an output position right.  Integer work only: the
+ * result is a function of the input alone.  daac_last_kernel() says "replace matches=.. out=.." in front of what the tuple call reported. */
+daac_status daac_replace_all(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                             const uint8_t *repl, const uint64_t *repl_offsets, size_t n_repl,
+                             uint8_t **dev_out, uint64_t *out_len, uint64_t *n_replaced);
+/* The same for a batch (the batch arguments and their rules are daac_scan_batch_device16's): every document is replaced as a haystack
+ * of its own — nothing crosses a boundary, a chain starts fresh at each document's 0.  Document i's result is
+ * dev_out[out_offsets[i], out_offsets[i+1]); *dev_out_offsets holds n + 1 u64 in device memory (daac_device_free).  n = 0: *dev_out =
+ * NULL and one offset, 0.  Note D names the document. */
+daac_status daac_replace_all_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                   void *stream, const uint8_t *repl, const uint64_t *repl_offsets, size_t n_repl,
+                                   uint8_t **dev_out, uint64_t **dev_out_offsets, uint64_t *out_len, uint64_t *n_replaced);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

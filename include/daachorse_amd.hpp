@@ -250,6 +250,33 @@ public:
         return scan_device(reinterpret_cast<const uint8_t *>(host_haystack.data()), host_haystack.size(), 0, nullptr);
     }
 
+    // replace_all over find_iter (Standard) / leftmost_find_iter (the leftmost kinds), spliced on the device (daac_replace_all[_batch]):
+    // one replacement for every match, or one per value (automata built without values: per pattern index).  A batch replaces every
+    // document as a haystack of its own.
+    std::string replace_all(std::string_view haystack, const std::vector<std::string> &replacements) const {
+        const Replacements r(replacements);
+        uint8_t *p = nullptr;
+        uint64_t n = 0, k = 0;
+        replace_check(daac_replace_all(h_.get(), replace_mode(), DAAC_ENGINE_AUTO, reinterpret_cast<const uint8_t *>(haystack.data()), haystack.size(), 0, nullptr,
+                                       r.blob(), r.offs.data(), replacements.size(), &p, &n, &k));
+        return replace_fetch(p, n);
+    }
+    std::vector<std::string> replace_all_batch(const std::vector<std::string> &docs, const std::vector<std::string> &replacements) const {
+        const Replacements r(replacements), d(docs);
+        uint8_t *p = nullptr;
+        uint64_t *po = nullptr, n = 0, k = 0;
+        replace_check(daac_replace_all_batch(h_.get(), replace_mode(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), docs.size(), 0, nullptr, r.blob(), r.offs.data(),
+                                             replacements.size(), &p, &po, &n, &k));
+        std::vector<uint64_t> o(docs.size() + 1);
+        const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
+        daac_device_free(po);
+        if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
+        const std::string all = replace_fetch(p, n);
+        std::vector<std::string> out;
+        for (size_t i = 0; i < docs.size(); ++i) out.push_back(all.substr(o[i], o[i + 1] - o[i]));
+        return out;
+    }
+
     // bytewise.rs:238-251, 353-375 / charwise.rs: steppers for text that arrives in pieces
     Stepper find_stepper() const { return open_stepper(DAAC_FIND); }
     Stepper find_overlapping_stepper() const { return open_stepper(DAAC_FIND_OVERLAPPING); }
@@ -283,6 +310,23 @@ private:
         if (st == DAAC_ERR_MATCH_KIND) throw PanicError("Error: match_kind must be standard.");
         if (st != DAAC_OK) throw PanicError(std::string("device scan failed: ") + daac_last_error());
         return DeviceMatches(p, n);
+    }
+    struct Replacements {   // strings as one blob + n + 1 offsets
+        std::string bytes;
+        std::vector<uint64_t> offs{0};
+        explicit Replacements(const std::vector<std::string> &v) { for (const auto &s : v) { bytes += s; offs.push_back(bytes.size()); } }
+        const uint8_t *blob() const { return reinterpret_cast<const uint8_t *>(bytes.data()); }
+    };
+    int replace_mode() const { return match_kind() == MatchKind::Standard ? DAAC_FIND : DAAC_LEFTMOST_FIND; }
+    static void replace_check(daac_status st) {
+        if (st != DAAC_OK) throw PanicError(std::string("replace_all failed: ") + daac_last_error());
+    }
+    static std::string replace_fetch(uint8_t *p, uint64_t n) {   // the device result to the host, and released
+        std::string out(n, '\0');
+        const daac_status st = daac_device_to_host(out.data(), p, n);
+        daac_device_free(p);
+        if (st != DAAC_OK) throw PanicError(daac_last_error());
+        return out;
     }
     Stepper open_stepper(int mode) const {
         daac_stream *st = nullptr;

@@ -104,6 +104,14 @@ extern "C" {
     /// ... and all documents' tuples as one CSR list in device memory (ends relative to the document)
     pub fn daac_scan_batch_device16(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
                                     stream: *mut c_void, dev_out: *mut *mut daac_match16, dev_doc_offsets: *mut *mut u64, total: *mut u64) -> i32;
+    /// replace_all over find_iter / leftmost_find_iter, spliced on the device: replacement i = repl[repl_offsets[i], repl_offsets[i+1])
+    /// (n_repl == 1: one for every match, otherwise indexed by the match's value); the result stays in device memory
+    pub fn daac_replace_all(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, len: usize, hay_is_device: i32, stream: *mut c_void,
+                            repl: *const u8, repl_offsets: *const u64, n_repl: usize, dev_out: *mut *mut u8, out_len: *mut u64, n_replaced: *mut u64) -> i32;
+    /// ... and for a batch: document i's result is dev_out[out_offsets[i], out_offsets[i+1])
+    pub fn daac_replace_all_batch(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                                  stream: *mut c_void, repl: *const u8, repl_offsets: *const u64, n_repl: usize, dev_out: *mut *mut u8,
+                                  dev_out_offsets: *mut *mut u64, out_len: *mut u64, n_replaced: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
