@@ -124,6 +124,10 @@ def lib():
     L.daac_replace_all.restype = C.c_int
     L.daac_replace_all_batch.argtypes = [vp, C.c_int, C.c_int, u8p, vp, sz, C.c_int, vp, vp, vp, sz, P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
     L.daac_replace_all_batch.restype = C.c_int
+    L.daac_tokenize.argtypes = [vp, C.c_int, C.c_int, u8p, sz, C.c_int, vp, C.c_int, C.c_uint32, P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokenize.restype = C.c_int
+    L.daac_tokenize_batch.argtypes = [vp, C.c_int, C.c_int, u8p, vp, sz, C.c_int, vp, C.c_int, C.c_uint32, P(vp), P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokenize_batch.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

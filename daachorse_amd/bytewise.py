@@ -41,6 +41,14 @@ class Engine(enum.IntEnum):
     Pfx = 4
 
 
+class Gap(enum.IntEnum):
+    """daac_gap: what tokenize makes of the text between two matches"""
+    Skip = 0    # nothing
+    Unk = 1     # one token per non-empty gap
+    Bytes = 2   # one token per byte, id = gap_id + the byte
+    Chars = 3   # one token per UTF-8 code point (a cut in front of every byte that is no continuation byte)
+
+
 class Match:
     """src/lib.rs:286-320"""
     __slots__ = ("_s", "_e", "_v")
@@ -116,6 +124,7 @@ MATCH16_DTYPE = np.dtype([("end", "<u8"), ("length", "<u4"), ("value", "<u4")]) 
 MATCH8_DTYPE = np.dtype([("value", "<u4"), ("end_len", "<u4")])  # daac_match8: end relative to the run's base | length << end_bits
 OUTPUT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("parent", "<u4")])  # an output record (a pattern's "slot")
 PATTERN_COUNT_DTYPE = np.dtype([("value", "<u4"), ("length", "<u4"), ("count", "<u8")])
+SPAN_DTYPE = np.dtype(("<u8", (2,)))  # a token's {start, end}: an array of it has shape [T, 2]
 SLOT_COUNT_DTYPE = np.dtype([("slot", "<u4"), ("count", "<u4")])  # daac_slot_count: a row of a batch's documents x slots matrix
 
 
@@ -600,6 +609,47 @@ class DoubleArrayAhoCorasick:
             dm.free()
             do.free()
         return [out[int(o[i]):int(o[i + 1])] for i in range(b.n)]
+
+    # ---- tokenize: the values of the matches of find_iter / leftmost_find_iter and the gaps between them as one id list
+    # (daac_tokenize[_batch]).  `gap` says what the text between matches becomes (Gap), `gap_id` the id it gets (Gap.Bytes: gap_id +
+    # the byte).  mode=None: Find for Standard handles, LeftmostFind otherwise.
+    def tokenize(self, haystack, gap=Gap.Unk, gap_id=0, spans=False, mode=None, engine=Engine.Auto, stream=None, device=False):
+        """-> ids (np.uint32[T]), or (ids, spans) with spans=True (np.uint64[T, 2], {start, end} in bytes); device=True: the same as
+        DeviceMatches (to_numpy / free), left in device memory"""
+        h = _Haystack(haystack)
+        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize(self._h, self._replace_mode(mode), int(engine), h.ptr, h.len, h.is_device, stream, int(gap), int(gap_id),
+                                            C.byref(ids), C.byref(sp) if spans else None, C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        return self._token_result(out, k.value, device)
+
+    def tokenize_batch(self, docs, gap=Gap.Unk, gap_id=0, spans=False, mode=None, engine=Engine.Auto, stream=None, device=False):
+        """-> (ids, offsets) or (ids, spans, offsets): every document is tokenized as a haystack of its own, document i's tokens are
+        [offsets[i], offsets[i+1]) (np.uint64[n + 1]) and its spans count from its first byte; device=True: DeviceMatches for ids and
+        spans, DeviceOffsets for offsets"""
+        b = _Batch(docs)
+        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_batch(self._h, self._replace_mode(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream, int(gap),
+                                                  int(gap_id), C.byref(ids), C.byref(sp) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        out.append(DeviceOffsets(offs.value, b.n + 1))
+        return self._token_result(out, k.value, device)
+
+    @staticmethod
+    def _token_result(out, n_matches, device):
+        out[0].n_matches = n_matches
+        if not device:
+            dev = out
+            try:
+                out = [o.to_numpy() for o in dev]
+            finally:
+                for o in dev:
+                    o.free()
+        return out[0] if len(out) == 1 else tuple(out)
 
 
 class _Replacements:

@@ -1,0 +1,194 @@
+// C ABI (include/daachorse_amd.h), part 9: tokenize on the device (daac_tokenize, daac_tokenize_batch).
+// The tuple list comes from the calls that already produce it (daac_scan_device16, daac_scan_batch_device16: their engines, refusals,
+// note D and max_result_bytes rule are this call's); the kernels are tokenize_kernels.hip.  This file validates, stages a host haystack
+// once, counts the tokens (two exclusive sums and one read-back), allocates the result and runs the write pass.
+#include "api_internal.hpp"
+#include "tokenize.hpp"
+
+namespace {
+
+// Everything that is decided before a device is touched: statuses 1, 6 and 5, in that order.
+daac_status tokenize_precheck(const daac_pma *pma, int mode, int gap, uint32_t gap_id, bool outs_ok) {
+    if (!pma || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (gap < DAAC_GAP_SKIP || gap > DAAC_GAP_CHARS) { set_error("gap is none of DAAC_GAP_SKIP, _UNK, _BYTES, _CHARS"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (gap == DAAC_GAP_BYTES && gap_id > 0xFFFFFFFFu - 255u) { set_error("DAAC_GAP_BYTES: gap_id + 255 does not fit 32 bits"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (mode == DAAC_FIND_OVERLAPPING || mode == DAAC_FIND_OVERLAPPING_NO_SUFFIX) {
+        set_error("tokenize serves DAAC_FIND and DAAC_LEFTMOST_FIND: overlapping matches have no gaps");
+        return DAAC_ERR_UNSUPPORTED;
+    }
+    return check_mode_kind(pma, mode);
+}
+
+struct TupleList {   // what the tuple calls hand out, released with the call
+    void *list = nullptr;
+    uint64_t *doc_first = nullptr;
+    hipStream_t s = nullptr;
+    ~TupleList() { dev_free(list, s); dev_free(doc_first, s); }
+};
+
+// The tokens of `text` (device, `len` bytes) with the k tuples of `tl`; a batch (d_doc_off != NULL) also gets its tok_offsets.
+daac_status tokens(const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k, const unsigned long long *d_doc_off, uint64_t n_docs, int gap,
+                   uint32_t gap_id, hipStream_t stream, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens) {
+    TokenizeArgs a{};
+    a.hay = text;
+    a.len = len;
+    a.seg = static_cast<const uint4 *>(tl.list);
+    a.k = k;
+    a.gap = gap;
+    a.gap_id = gap_id;
+    a.tiles = len / kTokTile + 1;
+    // {flagged bytes, empty matches}, a single haystack's two offsets, A, E, the three per-tile arrays, the sums' scratch
+    const uint64_t m = k + 1, tl1 = a.tiles + 1;
+    DevBuf work;
+    HIP_TRY(work.alloc((4 + 2 + k + m + 3 * tl1 + exclusive_scan_scratch(std::max(m, tl1))) * sizeof(unsigned long long), stream));
+    unsigned long long *hdr = static_cast<unsigned long long *>(work.p);
+    unsigned long long *pair = hdr + 4;
+    a.aend = pair + 2;
+    a.epre = a.aend + k;
+    a.tile_lo = a.epre + m;
+    a.tile_doc = a.tile_lo + tl1;
+    a.tile_cnt = a.tile_doc + tl1;
+    unsigned long long *scan_scratch = a.tile_cnt + tl1;
+    const unsigned long long one_doc[2] = {0, len};
+    if (d_doc_off) {
+        a.doc_first = reinterpret_cast<const unsigned long long *>(tl.doc_first);
+        a.doc_off = d_doc_off;
+        a.n_docs = n_docs;
+    } else {
+        HIP_TRY(hipMemcpyAsync(pair, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+        a.doc_off = pair;
+        a.n_docs = 1;
+    }
+    HIP_TRY(launch_tokenize_prep(a, stream));
+    HIP_TRY(launch_exclusive_scan(a.epre, m, hdr + 1, scan_scratch, stream));
+    HIP_TRY(launch_tokenize_count(a, stream));
+    HIP_TRY(launch_exclusive_scan(a.tile_cnt, tl1, hdr, scan_scratch, stream));
+    unsigned long long *pin = reinterpret_cast<unsigned long long *>(pinned_words());
+    unsigned long long local[2];
+    unsigned long long *h = pin ? pin : local;
+    HIP_TRY(hipMemcpyAsync(h, hdr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t flagged = h[0];
+    a.n_empty = h[1];
+    if (flagged > len || a.n_empty > k) { set_error("the token count does not fit the text and its matches"); return DAAC_ERR_DEVICE; }   // (never seen)
+    const uint64_t total = flagged + a.n_empty;
+    const uint64_t per_token = sizeof(uint32_t) + (dev_spans ? 2 * sizeof(uint64_t) : 0);
+    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
+        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
+        return DAAC_ERR_AUTOMATON_SCALE;
+    }
+    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
+    void *ids = nullptr, *spans = nullptr, *tok_off = nullptr;
+    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
+    auto g_ids = guard(ids);
+    if (total && dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
+    auto g_spans = guard(spans);
+    if (d_doc_off) HIP_TRY(dev_malloc(&tok_off, (n_docs + 1) * sizeof(uint64_t), stream));
+    auto g_off = guard(tok_off);
+    a.ids = static_cast<uint32_t *>(ids);
+    a.spans = static_cast<unsigned long long *>(spans);
+    a.tok_offsets = static_cast<unsigned long long *>(tok_off);
+    if (total || tok_off) HIP_TRY(launch_tokenize_write(a, total, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
+    g_last_kernel = "tokenize matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
+    *dev_ids = static_cast<uint32_t *>(g_ids.release());
+    if (dev_spans) *dev_spans = static_cast<uint64_t *>(g_spans.release());
+    if (dev_tok_offsets) *dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
+    *n_tokens = total;
+    return DAAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, int gap, uint32_t gap_id,
+                          uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches) {
+    PmaScope scope_(pma);
+    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, dev_ids && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    void *staged = nullptr;
+    const uint8_t *text = hay;
+    if (!hay_is_device && len) {   // the passes read the text on the device: the whole haystack, once
+        if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    TupleList tl;
+    tl.s = stream;
+    uint64_t k = 0;
+    if ((st = daac_scan_device16(pma, mode, engine, len ? text : nullptr, len, 1, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &k)) != DAAC_OK) return st;
+    if ((st = tokens(text, len, tl, k, nullptr, 0, gap, gap_id, stream, dev_ids, dev_spans, nullptr, n_tokens)) != DAAC_OK) return st;
+    *n_matches = k;
+    return DAAC_OK;
+}
+
+daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
+                                int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens,
+                                uint64_t *n_matches) {
+    PmaScope scope_(pma);
+    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    // the batch calls' own argument rules
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *dev_tok_offsets = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    TupleList tl;
+    tl.s = stream;
+    uint64_t k = 0;
+    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
+        if ((st = daac_scan_batch_device16(pma, mode, engine, hay, offsets, 0, hay_is_device, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
+        *dev_tok_offsets = tl.doc_first;
+        tl.doc_first = nullptr;
+        g_last_kernel = "tokenize matches=0 tokens=0 " + g_last_kernel;
+        return DAAC_OK;
+    }
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    // documents [offsets[0], offsets[n]) on the device, with their offsets
+    void *staged = nullptr;
+    const uint8_t *dev_hay = hay;
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
+    DevBuf off_buf;
+    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
+    if (!hay_is_device) {
+        ends[0] = offsets[0];
+        ends[1] = offsets[n];
+        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    if (!hay_is_device) {
+        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        d_off = static_cast<const unsigned long long *>(off_buf.p);
+    }
+    if ((st = daac_scan_batch_device16(pma, mode, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream_,
+                                       reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
+    if (hay_is_device) {   // (validated by the tuple call: non-decreasing)
+        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if ((st = tokens(dev_hay + ends[0], ends[1] - ends[0], tl, k, d_off, n, gap, gap_id, stream, dev_ids, dev_spans, dev_tok_offsets, n_tokens)) != DAAC_OK) return st;
+    *n_matches = k;
+    return DAAC_OK;
+}
+
+}  // extern "C"

@@ -46,7 +46,9 @@ extern "C" {
  *   (6, likewise: daac_slot_count / daac_scan_histogram_batch — per-document pattern counts of a batch, as a CSR matrix — and the
  *      options batch_hist_wave_max, batch_hist_sort_max.)
  *   (6, likewise: daac_replace_all / daac_replace_all_batch — the text with every match of find_iter / leftmost_find_iter replaced,
- *      spliced on the device.) */
+ *      spliced on the device.)
+ *   (6, likewise: daac_tokenize / daac_tokenize_batch and the enum daac_gap — the matches' values and the gaps between them as one token
+ *      id list, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -415,6 +417,45 @@ daac_status daac_replace_all(daac_pma *pma, int mode, int engine, const uint8_t 
 daac_status daac_replace_all_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
                                    void *stream, const uint8_t *repl, const uint64_t *repl_offsets, size_t n_repl,
                                    uint8_t **dev_out, uint64_t **dev_out_offsets, uint64_t *out_len, uint64_t *n_replaced);
+
+/* ---- tokenize: match values and gap tokens as an id list ---------------------------------------------------------------------------
+ * With m_0 .. m_{k-1} the matches the iterator of `mode` reports on hay (ordered, disjoint, positions in bytes), the gaps are
+ * g_0 = [0, start_0), g_i = [end_{i-1}, start_i), g_k = [end_{k-1}, len) (no match: the one gap [0, len)), and the token sequence is
+ * tok(g_0), m_0, tok(g_1), m_1, .., m_{k-1}, tok(g_k).  A match token is {id = value, start, end}; an empty match ("" among the patterns)
+ * is a token with start == end and separates two gaps like any other.  What a gap [a, b) contributes is `gap`'s choice: */
+typedef enum {
+    DAAC_GAP_SKIP = 0,  /* nothing */
+    DAAC_GAP_UNK = 1,   /* nothing if a == b, else one token {gap_id, a, b} */
+    DAAC_GAP_BYTES = 2, /* one token per byte p: {gap_id + hay[p], p, p + 1} (byte fallback) */
+    DAAC_GAP_CHARS = 3  /* the gap cut at a, at every p in (a, b) with (hay[p] & 0xC0) != 0x80, and at b: one {gap_id, c_j, c_j+1} per piece —
+                         * one unknown token per UTF-8 code point; the rule looks at single bytes only, so it is defined for any bytes, and
+                         * a gap that begins with continuation bytes still starts a token at a */
+} daac_gap;
+/* Modes: DAAC_FIND on Standard automata, DAAC_LEFTMOST_FIND on the leftmost kinds, bytewise and charwise handles.  *dev_ids holds
+ * *n_tokens u32 in device memory (NULL when there are none); dev_spans may be NULL (not wanted), otherwise *dev_spans holds 2 * n_tokens
+ * u64, {start, end} per token; *n_matches = k.  Both buffers are released with daac_device_free and copied with daac_device_to_host.
+ * The call returns after the stream has finished.
+ * Decided before a device is touched — a NULL dev_ids, n_tokens or n_matches, a gap outside 0..3, DAAC_GAP_BYTES with gap_id >
+ * 0xFFFFFFFF - 255: 1; the overlapping modes: 6; a MatchKind mismatch: 5.  The tuple list is daac_scan_device16's (the batch:
+ * daac_scan_batch_device16's): its engines and their refusals, note D (6) and the max_result_bytes rule of the list are this call's; a
+ * result above max_result_bytes (4 bytes a token, 16 more with spans) answers 2 before it is allocated.  A host haystack is copied to
+ * the device once.
+ * Method: the text is cut into tiles of 4 KiB, a lane takes 16 bytes.  From the matches and document beginnings that touch its bytes
+ * (found by one binary search per tile and one per lane inside the tile's range) and the gap rule a lane derives the 16-bit mask of
+ * bytes at which a token begins; a count pass sums the masks per tile, an exclusive sum gives the tiles' bases, and after one read-back
+ * of the totals the result is allocated and a write pass places ids and spans by wave and workgroup prefix sums.  Empty matches are
+ * placed by an exclusive sum over the match list.  No atomics, integer work only: the result is a function of the input alone.
+ * daac_last_kernel() says "tokenize matches=.. tokens=.." in front of what the tuple call reported. */
+daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                          int gap, uint32_t gap_id,
+                          uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches);
+/* The same for a batch (the batch arguments and their rules are daac_scan_batch_device16's): every document is tokenized as a haystack
+ * of its own — no gap crosses a boundary, positions are relative to the document's first byte.  Document i's tokens are
+ * [tok_offsets[i], tok_offsets[i+1]); *dev_tok_offsets (never NULL as an argument) holds n + 1 u64 in device memory (daac_device_free).
+ * n = 0: *dev_ids = NULL and one offset, 0.  Note D names the document. */
+daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                void *stream, int gap, uint32_t gap_id,
+                                uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens, uint64_t *n_matches);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

@@ -277,6 +277,30 @@ public:
         return out;
     }
 
+    // tokenize over find_iter (Standard) / leftmost_find_iter (the leftmost kinds) on the device (daac_tokenize[_batch]): the matches'
+    // values and what `gap` makes of the text between them, as one id list.  A batch tokenizes every document as a haystack of its own
+    // and returns the ids of all documents with n + 1 offsets into them.
+    std::vector<uint32_t> tokenize(std::string_view haystack, daac_gap gap = DAAC_GAP_UNK, uint32_t gap_id = 0) const {
+        uint32_t *p = nullptr;
+        uint64_t n = 0, k = 0;
+        tokenize_check(daac_tokenize(h_.get(), replace_mode(), DAAC_ENGINE_AUTO, reinterpret_cast<const uint8_t *>(haystack.data()), haystack.size(), 0, nullptr,
+                                     gap, gap_id, &p, nullptr, &n, &k));
+        return tokenize_fetch(p, n);
+    }
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> tokenize_batch(const std::vector<std::string> &docs, daac_gap gap = DAAC_GAP_UNK,
+                                                                            uint32_t gap_id = 0) const {
+        const Replacements d(docs);
+        uint32_t *p = nullptr;
+        uint64_t *po = nullptr, n = 0, k = 0;
+        tokenize_check(daac_tokenize_batch(h_.get(), replace_mode(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), docs.size(), 0, nullptr, gap, gap_id, &p, nullptr,
+                                           &po, &n, &k));
+        std::vector<uint64_t> o(docs.size() + 1);
+        const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
+        daac_device_free(po);
+        if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
+        return {tokenize_fetch(p, n), std::move(o)};
+    }
+
     // bytewise.rs:238-251, 353-375 / charwise.rs: steppers for text that arrives in pieces
     Stepper find_stepper() const { return open_stepper(DAAC_FIND); }
     Stepper find_overlapping_stepper() const { return open_stepper(DAAC_FIND_OVERLAPPING); }
@@ -324,6 +348,16 @@ private:
     static std::string replace_fetch(uint8_t *p, uint64_t n) {   // the device result to the host, and released
         std::string out(n, '\0');
         const daac_status st = daac_device_to_host(out.data(), p, n);
+        daac_device_free(p);
+        if (st != DAAC_OK) throw PanicError(daac_last_error());
+        return out;
+    }
+    static void tokenize_check(daac_status st) {
+        if (st != DAAC_OK) throw PanicError(std::string("tokenize failed: ") + daac_last_error());
+    }
+    static std::vector<uint32_t> tokenize_fetch(uint32_t *p, uint64_t n) {   // the device result to the host, and released
+        std::vector<uint32_t> out(n);
+        const daac_status st = daac_device_to_host(out.data(), p, n * sizeof(uint32_t));
         daac_device_free(p);
         if (st != DAAC_OK) throw PanicError(daac_last_error());
         return out;

@@ -112,6 +112,14 @@ extern "C" {
     pub fn daac_replace_all_batch(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
                                   stream: *mut c_void, repl: *const u8, repl_offsets: *const u64, n_repl: usize, dev_out: *mut *mut u8,
                                   dev_out_offsets: *mut *mut u64, out_len: *mut u64, n_replaced: *mut u64) -> i32;
+    /// tokenize over find_iter / leftmost_find_iter on the device: the matches' values and what `gap` (0 skip, 1 unk, 2 bytes, 3 chars)
+    /// makes of the text between them; dev_ids: n_tokens u32, dev_spans (may be null): 2 * n_tokens u64, both in device memory
+    pub fn daac_tokenize(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, len: usize, hay_is_device: i32, stream: *mut c_void,
+                         gap: i32, gap_id: u32, dev_ids: *mut *mut u32, dev_spans: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
+    /// ... and for a batch: document i's tokens are [tok_offsets[i], tok_offsets[i+1]), spans count from the document's first byte
+    pub fn daac_tokenize_batch(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                               stream: *mut c_void, gap: i32, gap_id: u32, dev_ids: *mut *mut u32, dev_spans: *mut *mut u64,
+                               dev_tok_offsets: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
