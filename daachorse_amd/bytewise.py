@@ -639,6 +639,49 @@ class DoubleArrayAhoCorasick:
         out.append(DeviceOffsets(offs.value, b.n + 1))
         return self._token_result(out, k.value, device)
 
+    # ---- tokenize_unigram: the segmentation whose pieces' scores sum highest (daac_tokenize_unigram[_batch]; Standard automata).
+    # `scores`: float32, indexed by match value; `unk_score`: the score of an unknown piece, which `gap` makes a byte (Gap.Bytes, id
+    # gap_id + the byte) or a UTF-8 code point (Gap.Chars, id gap_id).  One lane walks one document: made for batches of short documents.
+    @staticmethod
+    def _scores(scores):
+        a = np.ascontiguousarray(scores)
+        if a.ndim != 1 or a.dtype.kind not in "fiu":
+            raise DaachorseError(1, "scores must be a one-dimensional array of numbers")
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+    def tokenize_unigram(self, haystack, scores, unk_score, gap=Gap.Chars, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
+        """-> (ids, score), or (ids, spans, score) with spans=True: np.uint32[T], np.uint64[T, 2] ({start, end} in bytes) and the path's
+        score, a np.float32; device=True: ids and spans as DeviceMatches (to_numpy / free), left in device memory"""
+        h = _Haystack(haystack)
+        sc = self._scores(scores)
+        ids, sp, n, k, score = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _ffi.check(_ffi.lib().daac_tokenize_unigram(self._h, int(engine), h.ptr, h.len, h.is_device, stream, sc.ctypes.data if sc.size else None, sc.size,
+                                                    C.c_float(unk_score), int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None, C.byref(n),
+                                                    C.byref(k), C.byref(score)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        res = self._token_result(out, k.value, device)
+        return (res if spans else (res,)) + (np.float32(score.value),)
+
+    def tokenize_unigram_batch(self, docs, scores, unk_score, gap=Gap.Chars, gap_id=0, spans=False, doc_scores=False, engine=Engine.Auto, stream=None,
+                               device=False):
+        """-> (ids, offsets), with spans=True (ids, spans, offsets), with doc_scores=True one more at the end: np.float32[n], every
+        document's score.  Document i's tokens are [offsets[i], offsets[i+1]); device=True: DeviceMatches / DeviceOffsets"""
+        b = _Batch(docs)
+        sc = self._scores(scores)
+        ids, sp, offs, ds, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_unigram_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, sc.ctypes.data if sc.size else None,
+                                                          sc.size, C.c_float(unk_score), int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
+                                                          C.byref(offs), C.byref(ds) if doc_scores else None, C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        out.append(DeviceOffsets(offs.value, b.n + 1))
+        if doc_scores:
+            out.append(DeviceMatches(ds.value, b.n if ds.value else 0, np.dtype(np.float32)))
+        return self._token_result(out, k.value, device)
+
     @staticmethod
     def _token_result(out, n_matches, device):
         out[0].n_matches = n_matches

@@ -1,0 +1,235 @@
+// C ABI (include/daachorse_amd.h), part 10: the best-scoring segmentation of a text or a batch on the device (daac_tokenize_unigram,
+// daac_tokenize_unigram_batch).  The piece lattice is the tuple CSR of daac_scan_batch_device16(DAAC_FIND_OVERLAPPING): its engines,
+// refusals and max_result_bytes rule are this call's; the kernels are unigram_kernels.hip.  This file validates, stages a host text once,
+// copies the scores, runs the forward and count passes, sums the counts (one read-back), allocates the result and runs the write pass.
+// A single haystack is a batch of one document.
+#include <cmath>
+
+#include "api_internal.hpp"
+#include "unigram.hpp"
+
+namespace {
+
+// |score| <= kUniMaxScore: a path has fewer than 2^32 edges (a document of 2^32 - 1 bytes or more is refused), so no sum of them exceeds
+// 2^32 * 1e20 < 4.3e29 in magnitude and rounding cannot lift it to float32's 3.4e38: best[] never overflows to an infinity.
+constexpr float kUniMaxScore = 1e20f;
+constexpr uint64_t kUniMaxDoc = 0xFFFFFFFFull;   // bytes of a document: an edge's length is kept in 32 bits
+
+bool score_ok(float s) { return std::isfinite(s) && std::fabs(s) <= kUniMaxScore; }
+
+// Status 1, then status 5, before a device is touched.
+daac_status unigram_precheck(const daac_pma *pma, const float *scores, size_t n_scores, float unk_score, int gap, uint32_t gap_id, bool outs_ok) {
+    if (!pma || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (gap != DAAC_GAP_BYTES && gap != DAAC_GAP_CHARS) { set_error("gap is neither DAAC_GAP_BYTES nor DAAC_GAP_CHARS: the unknown edges must reach the text's end"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (gap == DAAC_GAP_BYTES && gap_id > 0xFFFFFFFFu - 255u) { set_error("DAAC_GAP_BYTES: gap_id + 255 does not fit 32 bits"); return DAAC_ERR_INVALID_ARGUMENT; }
+    const std::vector<daac::OutputRec> &outs = pma->charwise ? pma->chost.outputs : pma->host.outputs;
+    uint64_t need = 0;   // the largest value + 1
+    for (const daac::OutputRec &o : outs) need = std::max<uint64_t>(need, static_cast<uint64_t>(o.value) + 1);
+    if (n_scores < need) { set_error("n_scores = " + std::to_string(n_scores) + " does not cover the largest match value, " + std::to_string(need - 1)); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n_scores && !scores) { set_error("scores is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (!score_ok(unk_score)) { set_error("unk_score is NaN, infinite or above 1e20 in magnitude"); return DAAC_ERR_INVALID_ARGUMENT; }
+    for (size_t i = 0; i < n_scores; ++i)
+        if (!score_ok(scores[i])) { set_error("scores[" + std::to_string(i) + "] is NaN, infinite or above 1e20 in magnitude"); return DAAC_ERR_INVALID_ARGUMENT; }
+    return DAAC_OK;
+}
+
+daac_status unigram_kind(const daac_pma *pma) { return check_mode_kind(pma, DAAC_FIND_OVERLAPPING); }
+
+daac_status doc_too_long(uint64_t d, uint64_t len) {
+    set_error("document " + std::to_string(d) + " has " + std::to_string(len) + " bytes: tokenize_unigram walks a document on one lane and serves fewer than 2^32 - 1 bytes");
+    return DAAC_ERR_UNSUPPORTED;
+}
+
+struct Outs {   // the caller's out-pointers; the optional ones may be NULL
+    uint32_t **dev_ids;
+    uint64_t **dev_spans;
+    uint64_t **dev_tok_offsets;   // NULL: a single haystack
+    float **dev_doc_scores;
+    float *score;                 // a single haystack's
+    uint64_t *n_tokens, *n_matches;
+};
+
+// `text`: byte 0 of document 0 on the device, `len` bytes; `d_off`: the n + 1 offsets on the device (n >= 1), `begin` = offsets[0].
+daac_status segment(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t begin, uint64_t len, const unsigned long long *d_off, uint64_t n, hipStream_t stream,
+                    const float *scores, size_t n_scores, float unk_score, int gap, uint32_t gap_id, const Outs &o) {
+    daac_match16 *list = nullptr;
+    uint64_t *doc_first = nullptr;
+    uint64_t k = 0;
+    daac_status st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream, &list, &doc_first, &k);
+    if (st != DAAC_OK) return st;
+    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
+    auto g_list = guard(list), g_first = guard(doc_first);
+
+    daac::UnigramArgs a{};
+    a.hay = dev_hay + begin;
+    a.seg = reinterpret_cast<const daac::UniTuple *>(list);
+    a.doc_first = reinterpret_cast<const unsigned long long *>(doc_first);
+    a.doc_off = d_off;
+    a.n_docs = n;
+    a.n_scores = n_scores;
+    a.unk_score = unk_score;
+    a.gap = gap;
+    a.gap_id = gap_id;
+    // back (8 bytes a position), best and the scores (4), a single haystack's tok_offsets, the total, the sum's scratch
+    const uint64_t pos = len + n, m = n + 1;
+    DevBuf work;
+    HIP_TRY(work.alloc(pos * sizeof(daac::UniBack) + (2 + m + exclusive_scan_scratch(m)) * sizeof(unsigned long long) + (pos + n_scores + n) * sizeof(float), stream));
+    a.back = static_cast<daac::UniBack *>(work.p);
+    unsigned long long *hdr = reinterpret_cast<unsigned long long *>(a.back + pos);
+    unsigned long long *own_off = hdr + 2;
+    unsigned long long *scan_scratch = own_off + m;
+    a.best = reinterpret_cast<float *>(scan_scratch + exclusive_scan_scratch(m));
+    float *d_scores = a.best + pos;
+    float *own_doc_scores = d_scores + n_scores;
+    if (n_scores) HIP_TRY(hipMemcpyAsync(d_scores, scores, n_scores * sizeof(float), hipMemcpyHostToDevice, stream));
+    a.scores = d_scores;
+
+    void *tok_off = nullptr, *doc_scores = nullptr;
+    if (o.dev_tok_offsets) HIP_TRY(dev_malloc(&tok_off, m * sizeof(uint64_t), stream));
+    auto g_off = guard(tok_off);
+    if (o.dev_doc_scores) HIP_TRY(dev_malloc(&doc_scores, n * sizeof(float), stream));
+    auto g_scores = guard(doc_scores);
+    a.tok_offsets = tok_off ? static_cast<unsigned long long *>(tok_off) : own_off;
+    a.doc_scores = doc_scores ? static_cast<float *>(doc_scores) : o.score ? own_doc_scores : nullptr;
+
+    HIP_TRY(daac::launch_unigram_forward(a, stream));
+    HIP_TRY(daac::launch_unigram_count(a, stream));
+    HIP_TRY(daac::launch_exclusive_scan(a.tok_offsets, m, hdr, scan_scratch, stream));
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, hdr, sizeof(total), hipMemcpyDeviceToHost, stream));
+    if (o.score) HIP_TRY(hipMemcpyAsync(o.score, a.doc_scores, sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (total > len) { set_error("the token count does not fit the text"); return DAAC_ERR_DEVICE; }   // (never seen: every edge has a byte)
+    const uint64_t per_token = sizeof(uint32_t) + (o.dev_spans ? 2 * sizeof(uint64_t) : 0);
+    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
+        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
+        return DAAC_ERR_AUTOMATON_SCALE;
+    }
+    void *ids = nullptr, *spans = nullptr;
+    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
+    auto g_ids = guard(ids);
+    if (total && o.dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
+    auto g_spans = guard(spans);
+    a.ids = static_cast<uint32_t *>(ids);
+    a.spans = static_cast<unsigned long long *>(spans);
+    if (total) HIP_TRY(daac::launch_unigram_write(a, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
+    g_last_kernel = "unigram docs=" + std::to_string(n) + " matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
+    *o.dev_ids = static_cast<uint32_t *>(g_ids.release());
+    if (o.dev_spans) *o.dev_spans = static_cast<uint64_t *>(g_spans.release());
+    if (o.dev_tok_offsets) *o.dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
+    if (o.dev_doc_scores) *o.dev_doc_scores = static_cast<float *>(g_scores.release());
+    *o.n_tokens = total;
+    *o.n_matches = k;
+    return DAAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+daac_status daac_tokenize_unigram(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, const float *scores, size_t n_scores,
+                                  float unk_score, int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches,
+                                  float *score) {
+    PmaScope scope_(pma);
+    daac_status st = unigram_precheck(pma, scores, n_scores, unk_score, gap, gap_id, dev_ids && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = unigram_kind(pma)) != DAAC_OK) return st;
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    if (score) *score = 0.0f;
+    if (len >= kUniMaxDoc) return doc_too_long(0, len);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    void *staged = nullptr;
+    const uint8_t *text = hay;
+    if (!hay_is_device && len) {   // the passes read the text on the device: the whole haystack, once
+        if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    DevBuf granule, off_buf;   // an empty text still gives the tuple call a buffer to point at
+    if (!len) {
+        HIP_TRY(granule.alloc(16, stream));
+        text = static_cast<const uint8_t *>(granule.p);
+    }
+    const unsigned long long one_doc[2] = {0, len};
+    HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
+    HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+    const Outs o{dev_ids, dev_spans, nullptr, nullptr, score, n_tokens, n_matches};
+    return segment(pma, engine, text, 0, len, static_cast<const unsigned long long *>(off_buf.p), 1, stream, scores, n_scores, unk_score, gap, gap_id, o);
+}
+
+daac_status daac_tokenize_unigram_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
+                                        const float *scores, size_t n_scores, float unk_score, int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans,
+                                        uint64_t **dev_tok_offsets, float **dev_doc_scores, uint64_t *n_tokens, uint64_t *n_matches) {
+    PmaScope scope_(pma);
+    daac_status st = unigram_precheck(pma, scores, n_scores, unk_score, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    // the batch calls' own argument rules
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = unigram_kind(pma)) != DAAC_OK) return st;
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *dev_tok_offsets = nullptr;
+    if (dev_doc_scores) *dev_doc_scores = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
+        daac_match16 *list = nullptr;
+        uint64_t *doc_first = nullptr;
+        uint64_t k = 0;
+        if ((st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, hay, offsets, 0, hay_is_device, stream_, &list, &doc_first, &k)) != DAAC_OK) return st;
+        *dev_tok_offsets = doc_first;
+        g_last_kernel = "unigram docs=0 matches=0 tokens=0 " + g_last_kernel;
+        return DAAC_OK;
+    }
+    if (!hay_is_device)
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] - offsets[i] >= kUniMaxDoc) return doc_too_long(i, offsets[i + 1] - offsets[i]);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    // documents [offsets[0], offsets[n]) on the device, with their offsets
+    void *staged = nullptr;
+    const uint8_t *dev_hay = hay;
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
+    DevBuf off_buf;
+    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
+    if (!hay_is_device) {
+        ends[0] = offsets[0];
+        ends[1] = offsets[n];
+        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    if (!hay_is_device) {
+        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    } else {   // the first and last offset size the scratch; a decreasing pair in between is the tuple call's to refuse
+        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ends[1] < ends[0]) { set_error("offsets decrease"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (ends[1] - ends[0] >= kUniMaxDoc) {   // only then can a document be too long: look at them all
+            std::vector<uint64_t> h(n + 1);
+            HIP_TRY(hipMemcpyAsync(h.data(), d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            for (size_t i = 0; i < n; ++i)
+                if (h[i + 1] >= h[i] && h[i + 1] - h[i] >= kUniMaxDoc) return doc_too_long(i, h[i + 1] - h[i]);
+        }
+    }
+    if (!hay_is_device) d_off = static_cast<const unsigned long long *>(off_buf.p);
+    const Outs o{dev_ids, dev_spans, dev_tok_offsets, dev_doc_scores, nullptr, n_tokens, n_matches};
+    return segment(pma, engine, dev_hay, ends[0], ends[1] - ends[0], d_off, n, stream, scores, n_scores, unk_score, gap, gap_id, o);
+}
+
+}  // extern "C"

@@ -48,7 +48,9 @@ extern "C" {
  *   (6, likewise: daac_replace_all / daac_replace_all_batch — the text with every match of find_iter / leftmost_find_iter replaced,
  *      spliced on the device.)
  *   (6, likewise: daac_tokenize / daac_tokenize_batch and the enum daac_gap — the matches' values and the gaps between them as one token
- *      id list, on the device.) */
+ *      id list, on the device.)
+ *   (6, likewise: daac_tokenize_unigram / daac_tokenize_unigram_batch — the segmentation whose pieces' scores sum highest, a Viterbi pass
+ *      over the tuple list of an overlapping scan, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -456,6 +458,56 @@ daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *ha
 daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
                                 void *stream, int gap, uint32_t gap_id,
                                 uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens, uint64_t *n_matches);
+
+/* ---- tokenize_unigram: the segmentation whose pieces' scores sum highest ----------------------------------------------------------------
+ * What the SentencePiece Unigram model and the minimum-cost lattice walk of a morphological analyser compute: not the longest match
+ * first, but the best path through the lattice of all dictionary pieces.  Inputs: a Standard automaton (bytewise or charwise), a text or
+ * a batch of documents, `scores` (n_scores float32, indexed by match value; a host array, copied once per call), `unk_score`, `gap`
+ * (DAAC_GAP_BYTES or DAAC_GAP_CHARS) and `gap_id`.  Every document is a problem of its own.  For a document doc of L bytes:
+ *   Nodes: the byte positions 0 .. L.
+ *   Match edges: every match (start, end, value) of find_overlapping_iter(doc) with start < end is an edge start -> end with score
+ *     scores[value] and id value.  Empty matches ("" among the patterns) are not edges.
+ *   Unknown edges: the cuts are 0, L and — DAAC_GAP_BYTES: every position; DAAC_GAP_CHARS: every p with (doc[p] & 0xC0) != 0x80 (the
+ *     single-byte rule of daac_gap, defined on any bytes).  Consecutive cuts c -> c' are an edge with score unk_score and id gap_id
+ *     (_CHARS) or gap_id + doc[c] (_BYTES).  The cuts chain from 0 to L, so L is always reachable.
+ *   Best score: best[0] = +0.0f.  For q = 1 .. L the incumbent starts at -inf with no edge; the candidates are visited in this order: the
+ *     match edges into q in the order find_overlapping_iter reports them, then the unknown edge into q if q is a cut.  A candidate's score
+ *     is the single float32 addition best[from] + score (round to nearest, nothing fused or reassociated) and replaces the incumbent only
+ *     when strictly greater (>): ties go to the earliest match in the reference's order and to a match before the unknown edge.  An edge
+ *     out of an unreachable node (-inf) is never recorded.
+ *   Result: the edges on the back-pointer path from L to 0, in text order; a token is {id, start, end} with byte positions relative to
+ *     the document, the document's score is best[L].  An empty document has no tokens and score +0.0f.
+ * With this order and the single addition the ids, the spans and the 32 bits of every score are a function of the input alone.
+ * Results follow daac_tokenize: *dev_ids holds *n_tokens u32 in device memory (NULL when there are none), dev_spans may be NULL (not
+ * wanted), otherwise 2 * n_tokens u64; *n_matches = the tuples of the lattice, empty matches included; `score` (host, may be NULL)
+ * receives best[L].  Buffers are released with daac_device_free.  The call returns after the stream has finished.  There is no mode: the
+ * lattice is DAAC_FIND_OVERLAPPING.
+ * Decided before a device is touched, in this order.  Status 1: a NULL dev_ids, n_tokens or n_matches (the batch: dev_tok_offsets too);
+ * a gap that is neither DAAC_GAP_BYTES nor DAAC_GAP_CHARS; DAAC_GAP_BYTES with gap_id > 0xFFFFFFFF - 255; n_scores not above the largest
+ * value among daac_pma_outputs; a score or unk_score that is NaN, infinite or above 1e20 in magnitude (a path has fewer than 2^32 edges,
+ * so with that bound no path sum can overflow float32 on any text the call accepts); the batch's own offset rules, as in
+ * daac_tokenize_batch.  Status 5: a leftmost automaton.  The tuple list is daac_scan_batch_device16's: its engines and their refusals
+ * (6) and the max_result_bytes rule of the list are this call's; a token list above max_result_bytes (4 bytes a token, 16 more with
+ * spans) answers 2 before it is allocated.  A host text is copied to the device once.
+ * Method: the unit of parallelism is the document — one lane walks one document, 64 documents to a wave, which is what these tokenizers
+ * are fed (words after the whitespace split, sentences: 10^5 .. 10^7 documents of 5 .. 300 bytes).  A forward pass walks q = 1 .. L
+ * through the document's tuples (their ends do not decrease) and stores best[q] and the winning edge {length, id} per position (12 bytes
+ * of scratch per byte of text); a count pass follows the back pointers from L, an exclusive sum of the counts gives tok_offsets and the
+ * total (one read-back), and a write pass follows them again and fills the document's range from the back.  No atomics.
+ * Limits: a wave takes as long as its longest document, and one long haystack runs on a single lane — daac_tokenize_unigram on a long
+ * text is correct and slow.  A document of 2^32 - 1 bytes or more answers 6.
+ * daac_last_kernel() says "unigram docs=.. matches=.. tokens=.." in front of what the tuple call reported. */
+daac_status daac_tokenize_unigram(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                                  const float *scores, size_t n_scores, float unk_score, int gap, uint32_t gap_id,
+                                  uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches, float *score);
+/* The same for a batch (the batch arguments and their rules are daac_scan_batch_device16's).  Document i's tokens are
+ * [tok_offsets[i], tok_offsets[i+1]); *dev_tok_offsets (never NULL as an argument) holds n + 1 u64 in device memory; dev_doc_scores may be
+ * NULL (not wanted), otherwise *dev_doc_scores holds n float32 in device memory (both: daac_device_free).  n = 0: *dev_ids = NULL, one
+ * offset, 0, and no scores. */
+daac_status daac_tokenize_unigram_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                        void *stream, const float *scores, size_t n_scores, float unk_score, int gap, uint32_t gap_id,
+                                        uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, float **dev_doc_scores,
+                                        uint64_t *n_tokens, uint64_t *n_matches);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

@@ -301,6 +301,31 @@ public:
         return {tokenize_fetch(p, n), std::move(o)};
     }
 
+    // The segmentation whose pieces' scores sum highest (daac_tokenize_unigram[_batch]; Standard automata): a Viterbi pass over the
+    // overlapping matches with `scores[value]` per match and `unk_score` per unknown piece (a byte, or a UTF-8 code point).  `score`
+    // receives the path's score.  A batch segments every document on its own and returns all ids with n + 1 offsets into them.
+    std::vector<uint32_t> tokenize_unigram(std::string_view haystack, const std::vector<float> &scores, float unk_score, daac_gap gap = DAAC_GAP_CHARS,
+                                           uint32_t gap_id = 0, float *score = nullptr) const {
+        uint32_t *p = nullptr;
+        uint64_t n = 0, k = 0;
+        tokenize_check(daac_tokenize_unigram(h_.get(), DAAC_ENGINE_AUTO, reinterpret_cast<const uint8_t *>(haystack.data()), haystack.size(), 0, nullptr,
+                                             scores.data(), scores.size(), unk_score, gap, gap_id, &p, nullptr, &n, &k, score));
+        return tokenize_fetch(p, n);
+    }
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> tokenize_unigram_batch(const std::vector<std::string> &docs, const std::vector<float> &scores,
+                                                                                    float unk_score, daac_gap gap = DAAC_GAP_CHARS, uint32_t gap_id = 0) const {
+        const Replacements d(docs);
+        uint32_t *p = nullptr;
+        uint64_t *po = nullptr, n = 0, k = 0;
+        tokenize_check(daac_tokenize_unigram_batch(h_.get(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), docs.size(), 0, nullptr, scores.data(), scores.size(),
+                                                   unk_score, gap, gap_id, &p, nullptr, &po, nullptr, &n, &k));
+        std::vector<uint64_t> o(docs.size() + 1);
+        const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
+        daac_device_free(po);
+        if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
+        return {tokenize_fetch(p, n), std::move(o)};
+    }
+
     // bytewise.rs:238-251, 353-375 / charwise.rs: steppers for text that arrives in pieces
     Stepper find_stepper() const { return open_stepper(DAAC_FIND); }
     Stepper find_overlapping_stepper() const { return open_stepper(DAAC_FIND_OVERLAPPING); }

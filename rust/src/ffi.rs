@@ -120,6 +120,16 @@ extern "C" {
     pub fn daac_tokenize_batch(pma: *mut daac_pma, mode: i32, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
                                stream: *mut c_void, gap: i32, gap_id: u32, dev_ids: *mut *mut u32, dev_spans: *mut *mut u64,
                                dev_tok_offsets: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
+    /// the segmentation whose pieces' scores sum highest (a Viterbi pass over the overlapping matches): scores is a host array indexed by
+    /// match value, gap is 2 (bytes) or 3 (chars); score (may be null) receives the path's score
+    pub fn daac_tokenize_unigram(pma: *mut daac_pma, engine: i32, hay: *const u8, len: usize, hay_is_device: i32, stream: *mut c_void,
+                                 scores: *const f32, n_scores: usize, unk_score: f32, gap: i32, gap_id: u32, dev_ids: *mut *mut u32,
+                                 dev_spans: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64, score: *mut f32) -> i32;
+    /// ... and for a batch: dev_doc_scores (may be null) receives n f32 in device memory
+    pub fn daac_tokenize_unigram_batch(pma: *mut daac_pma, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                                       stream: *mut c_void, scores: *const f32, n_scores: usize, unk_score: f32, gap: i32, gap_id: u32,
+                                       dev_ids: *mut *mut u32, dev_spans: *mut *mut u64, dev_tok_offsets: *mut *mut u64,
+                                       dev_doc_scores: *mut *mut f32, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
