@@ -133,6 +133,10 @@ def lib():
     L.daac_tokenize_unigram.restype = C.c_int
     L.daac_tokenize_unigram_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, vp, sz, C.c_float, C.c_int, C.c_uint32, P(vp), P(vp), P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
     L.daac_tokenize_unigram_batch.restype = C.c_int
+    L.daac_tokenize_bpe.argtypes = [vp, C.c_int, u8p, sz, C.c_int, vp, vp, sz, C.c_int, C.c_uint32, P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokenize_bpe.restype = C.c_int
+    L.daac_tokenize_bpe_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, vp, sz, C.c_int, C.c_uint32, P(vp), P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokenize_bpe_batch.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

@@ -682,6 +682,49 @@ class DoubleArrayAhoCorasick:
             out.append(DeviceMatches(ds.value, b.n if ds.value else 0, np.dtype(np.float32)))
         return self._token_result(out, k.value, device)
 
+    # ---- tokenize_bpe: byte-pair merging in rank order (daac_tokenize_bpe[_batch]; Standard automata) — tiktoken's byte_pair_merge for
+    # one piece of pre-split text.  `ranks`: uint32, indexed by match value (None: a piece's rank is its value; 0xFFFFFFFF: never the
+    # product of a merge); a part the vocabulary lacks becomes a byte (Gap.Bytes, id gap_id + the byte) or a UTF-8 code point (Gap.Chars,
+    # id gap_id).  One lane merges one document in up to L^2 / 2 steps: a document above option bpe_doc_max (4096) is refused.
+    @staticmethod
+    def _ranks(ranks):
+        if ranks is None:
+            return None
+        a = np.ascontiguousarray(ranks)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or a.size == 0 or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+            raise DaachorseError(1, "ranks must be None or a non-empty one-dimensional array of integers in 0 .. 0xFFFFFFFF")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def tokenize_bpe(self, haystack, ranks=None, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
+        """-> ids (np.uint32[T]), or (ids, spans) with spans=True (np.uint64[T, 2], {start, end} in bytes); device=True: the same as
+        DeviceMatches (to_numpy / free), left in device memory"""
+        h = _Haystack(haystack)
+        rk = self._ranks(ranks)
+        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_bpe(self._h, int(engine), h.ptr, h.len, h.is_device, stream, None if rk is None else rk.ctypes.data,
+                                                0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
+                                                C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        return self._token_result(out, k.value, device)
+
+    def tokenize_bpe_batch(self, docs, ranks=None, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
+        """-> (ids, offsets) or (ids, spans, offsets): every document is merged on its own, document i's tokens are
+        [offsets[i], offsets[i+1]) (np.uint64[n + 1]) and its spans count from its first byte; device=True: DeviceMatches for ids and
+        spans, DeviceOffsets for offsets"""
+        b = _Batch(docs)
+        rk = self._ranks(ranks)
+        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_bpe_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, None if rk is None else rk.ctypes.data,
+                                                      0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
+                                                      C.byref(offs), C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        out.append(DeviceOffsets(offs.value, b.n + 1))
+        return self._token_result(out, k.value, device)
+
     @staticmethod
     def _token_result(out, n_matches, device):
         out[0].n_matches = n_matches

@@ -86,7 +86,8 @@ const char *last_error_cstr();
                                             16384: the winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */ \
     X(batch_hist_wave_max, 2048, 0)      /* batch histograms: most records of a document that one wave sorts in LDS (at most 4096) */            \
     X(batch_hist_sort_max, 16384, 0)     /* ... and that one workgroup sorts (at most 32768: what 160 KB hold); above: dense counters in HBM;    \
-                                            both from tools/time_batch_hist.py's sweep (profiles/r12_batch_hist_time.json) */
+                                            both from tools/time_batch_hist.py's sweep (profiles/r12_batch_hist_time.json) */ \
+    X(bpe_doc_max, 4096, 0)              /* tokenize_bpe: longest document it merges (1 .. 65536); a longer one answers 6 */
 
 enum OptionId : int {
 #define X(NAME, DEF, UP) OPT_##NAME,

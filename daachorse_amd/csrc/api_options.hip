@@ -25,6 +25,10 @@ static bool option_value_ok(const char *name, int id, int64_t value) {
         set_error(std::string("option ") + name + " counts a document's records: it cannot be negative");
         return false;
     }
+    if (id == OPT_bpe_doc_max && (value < 1 || value > 65536)) {
+        set_error(std::string("option ") + name + " is the longest document tokenize_bpe merges, in bytes: 1 .. 65536");
+        return false;
+    }
     return true;
 }
 

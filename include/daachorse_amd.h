@@ -50,7 +50,9 @@ extern "C" {
  *   (6, likewise: daac_tokenize / daac_tokenize_batch and the enum daac_gap — the matches' values and the gaps between them as one token
  *      id list, on the device.)
  *   (6, likewise: daac_tokenize_unigram / daac_tokenize_unigram_batch — the segmentation whose pieces' scores sum highest, a Viterbi pass
- *      over the tuple list of an overlapping scan, on the device.) */
+ *      over the tuple list of an overlapping scan, on the device.)
+ *   (6, likewise: daac_tokenize_bpe / daac_tokenize_bpe_batch — the token ids of byte-pair merging in rank order over the same tuple
+ *      list, on the device — and the option bpe_doc_max.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -509,6 +511,57 @@ daac_status daac_tokenize_unigram_batch(daac_pma *pma, int engine, const uint8_t
                                         uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, float **dev_doc_scores,
                                         uint64_t *n_tokens, uint64_t *n_matches);
 
+/* ---- tokenize_bpe: byte-pair merging in rank order ----------------------------------------------------------------------------------------
+ * What tiktoken's byte_pair_merge computes for one piece of pre-split text (the cl100k / o200k, GPT-2, Llama and Mistral vocabularies):
+ * neither the longest match first nor a best-scoring path, but the parts left when neighbouring parts have been merged in the order of
+ * their ranks.  For "abcd" with "bc" ranked before "ab" and "bcd" in the vocabulary it gives a|bcd where longest-match-first gives
+ * ab|c|d.  Inputs: a Standard automaton (bytewise or charwise), a text or a batch of documents, `ranks` (n_ranks uint32, indexed by
+ * match value; a host array, copied once per call; ranks = NULL with n_ranks = 0: a piece's rank is its value), `gap` (DAAC_GAP_BYTES
+ * or DAAC_GAP_CHARS) and `gap_id`.  Every document is a problem of its own.  For a document doc of L bytes:
+ *   Pieces: piece(s, e) for 0 <= s < e <= L is the value v of the match (s, e, v) in find_overlapping_iter(doc); it is absent when there
+ *     is no such match (patterns are unique, so there is at most one).  Empty matches ("" among the patterns) are not pieces.
+ *     rank(s, e) is ranks[v], or v without a table.  A rank of 0xFFFFFFFF means the piece is never the product of a merge; such a piece
+ *     can still be an initial part.
+ *   Initial parts: the boundaries are the cuts of daac_gap — 0, L and — DAAC_GAP_BYTES: every position; DAAC_GAP_CHARS: every p with
+ *     (doc[p] & 0xC0) != 0x80 (the single-byte rule, defined on any bytes).  Consecutive boundaries delimit the parts.
+ *   Merge loop: with the live boundaries p_0 = 0 < p_1 < .. < p_k = L, among all i with piece(p_i, p_{i+2}) present and its rank not
+ *     0xFFFFFFFF take the smallest rank, on ties the smallest i; remove p_{i+1}; repeat until no such i exists.  Ranks are looked up by
+ *     the concatenated bytes, not by the pair (as tiktoken does; a merges.txt vocabulary keyed by pairs is another rule).
+ *   Result: one token per final part (p_i, p_{i+1}), in text order.  Its id is piece(p_i, p_{i+1}) when present; otherwise the part is
+ *     an initial part that the vocabulary lacks and its id is gap_id + doc[p_i] (_BYTES) or gap_id (_CHARS).  An absent initial part
+ *     still takes part in merges like any other part: piece is defined on byte ranges only.  A token is {id, start, end} with byte
+ *     positions relative to the document.  An empty document has no tokens.
+ * The result does not depend on the order of tuples that share an end: it is a function of the input alone.
+ * Results follow daac_tokenize: *dev_ids holds *n_tokens u32 in device memory (NULL when there are none), dev_spans may be NULL (not
+ * wanted), otherwise 2 * n_tokens u64; *n_matches = the tuples of the scan, empty matches included.  Buffers are released with
+ * daac_device_free.  The call returns after the stream has finished.  There is no mode: the pieces are DAAC_FIND_OVERLAPPING's.
+ * Decided before a device is touched, in this order.  Status 1: a NULL dev_ids, n_tokens or n_matches (the batch: dev_tok_offsets too);
+ * a gap that is neither DAAC_GAP_BYTES nor DAAC_GAP_CHARS; DAAC_GAP_BYTES with gap_id > 0xFFFFFFFF - 255; ranks == NULL with n_ranks != 0
+ * or the reverse; a non-NULL ranks whose n_ranks is not above the largest value among daac_pma_outputs; the batch's own offset rules, as
+ * in daac_tokenize_batch.  Status 5: a leftmost automaton.  Then the length cap: the merge loop scans a document's live parts once per
+ * merge, up to L^2 / 2 part visits on one lane, so a document longer than option bpe_doc_max (4096 — about 8.4 M visits; 1 .. 65536)
+ * answers 6 before a kernel of this call is launched, and the message names the document and says to pre-split the text (real BPE runs
+ * behind a pre-tokenizer split: its inputs are words).  Host offsets are checked before a device is touched, device offsets by one
+ * read-back of the first and last offset, and of all of them when those two are further apart than the cap.  The tuple list is
+ * daac_scan_batch_device16's: its engines and their refusals (6) and the max_result_bytes rule of the list are this call's; a token list
+ * above max_result_bytes (4 bytes a token, 16 more with spans) answers 2 before it is allocated.  A host text is copied to the device once.
+ * Method: the unit of parallelism is the document — one lane per document, 64 documents to a wave.  The lane indexes its tuples by end
+ * (piece(s, e) is then a look through the tuples that end at e), links the initial boundaries, caches the rank and value of every pair of
+ * neighbours and loops: a linear minimum over the live pairs, unlink, recompute the two neighbouring pairs (24 bytes of scratch per byte
+ * of text).  The live-part counts are summed to tok_offsets and the total (one read-back), and a write pass walks the links and fills
+ * the document's range.  No atomics, integer work only.
+ * daac_last_kernel() says "bpe docs=.. matches=.. tokens=.." in front of what the tuple call reported. */
+daac_status daac_tokenize_bpe(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                              const uint32_t *ranks, size_t n_ranks, int gap, uint32_t gap_id,
+                              uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches);
+/* The same for a batch (the batch arguments and their rules are daac_scan_batch_device16's).  Document i's tokens are
+ * [tok_offsets[i], tok_offsets[i+1]); *dev_tok_offsets (never NULL as an argument) holds n + 1 u64 in device memory (daac_device_free).
+ * n = 0: *dev_ids = NULL and one offset, 0. */
+daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                    void *stream, const uint32_t *ranks, size_t n_ranks, int gap, uint32_t gap_id,
+                                    uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets,
+                                    uint64_t *n_tokens, uint64_t *n_matches);
+
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
  * not be resident), byte 0 of the haystack is still `hay`.  For the overlapping modes any `begin` works (charwise:
@@ -621,6 +674,8 @@ void daac_stream_close(daac_stream *s);
  *   max_result_bytes (8 GiB)    largest match list daac_scan may materialise
  *   batch_piece (4096)          batches, find_overlapping modes: bytes of a document one lane scans (a piece; entered up to the halo early)
  *   batch_lane_max (16384)      batches, find_iter / leftmost_find_iter: longest document one lane walks; longer ones take the single-haystack path
+ *   bpe_doc_max (4096)          daac_tokenize_bpe[_batch]: the longest document, in bytes, the merge loop takes (its work on one lane grows with
+ *                               the square of the length); 1 .. 65536, any other value: status 1; a longer document answers 6
  *   batch_hist_wave_max (2048)  per-document pattern counts: most match records of a document that one wave sorts in LDS (clamped to 4096)
  *   batch_hist_sort_max (16384) ... and that one workgroup sorts (clamped to 32768, what 160 KB of LDS hold); documents with more take a row
  *                               of outputs_len counters in HBM.  Neither is read at upload; negative values are status 1.  The defaults are

@@ -326,6 +326,32 @@ public:
         return {tokenize_fetch(p, n), std::move(o)};
     }
 
+    // Byte-pair merging in rank order (daac_tokenize_bpe[_batch]; Standard automata): what tiktoken's byte_pair_merge gives for one piece
+    // of pre-split text.  `ranks[value]` is a piece's rank (empty: its value); a part the vocabulary lacks becomes a byte or a UTF-8 code
+    // point (`gap`).  A document above the handle's option bpe_doc_max is refused.  A batch merges every document on its own and returns
+    // all ids with n + 1 offsets into them.
+    std::vector<uint32_t> tokenize_bpe(std::string_view haystack, const std::vector<uint32_t> &ranks = {}, daac_gap gap = DAAC_GAP_BYTES,
+                                       uint32_t gap_id = 0) const {
+        uint32_t *p = nullptr;
+        uint64_t n = 0, k = 0;
+        tokenize_check(daac_tokenize_bpe(h_.get(), DAAC_ENGINE_AUTO, reinterpret_cast<const uint8_t *>(haystack.data()), haystack.size(), 0, nullptr,
+                                         ranks.empty() ? nullptr : ranks.data(), ranks.size(), gap, gap_id, &p, nullptr, &n, &k));
+        return tokenize_fetch(p, n);
+    }
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> tokenize_bpe_batch(const std::vector<std::string> &docs, const std::vector<uint32_t> &ranks = {},
+                                                                                daac_gap gap = DAAC_GAP_BYTES, uint32_t gap_id = 0) const {
+        const Replacements d(docs);
+        uint32_t *p = nullptr;
+        uint64_t *po = nullptr, n = 0, k = 0;
+        tokenize_check(daac_tokenize_bpe_batch(h_.get(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), docs.size(), 0, nullptr,
+                                               ranks.empty() ? nullptr : ranks.data(), ranks.size(), gap, gap_id, &p, nullptr, &po, &n, &k));
+        std::vector<uint64_t> o(docs.size() + 1);
+        const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
+        daac_device_free(po);
+        if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
+        return {tokenize_fetch(p, n), std::move(o)};
+    }
+
     // bytewise.rs:238-251, 353-375 / charwise.rs: steppers for text that arrives in pieces
     Stepper find_stepper() const { return open_stepper(DAAC_FIND); }
     Stepper find_overlapping_stepper() const { return open_stepper(DAAC_FIND_OVERLAPPING); }

@@ -130,6 +130,15 @@ extern "C" {
                                        stream: *mut c_void, scores: *const f32, n_scores: usize, unk_score: f32, gap: i32, gap_id: u32,
                                        dev_ids: *mut *mut u32, dev_spans: *mut *mut u64, dev_tok_offsets: *mut *mut u64,
                                        dev_doc_scores: *mut *mut f32, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
+    /// byte-pair merging in rank order over the overlapping matches (tiktoken's byte_pair_merge): ranks is a host array indexed by match
+    /// value (null with n_ranks 0: a piece's rank is its value), gap is 2 (bytes) or 3 (chars); a document above option bpe_doc_max: 6
+    pub fn daac_tokenize_bpe(pma: *mut daac_pma, engine: i32, hay: *const u8, len: usize, hay_is_device: i32, stream: *mut c_void,
+                             ranks: *const u32, n_ranks: usize, gap: i32, gap_id: u32, dev_ids: *mut *mut u32, dev_spans: *mut *mut u64,
+                             n_tokens: *mut u64, n_matches: *mut u64) -> i32;
+    /// ... and for a batch: document i's tokens are [tok_offsets[i], tok_offsets[i+1])
+    pub fn daac_tokenize_bpe_batch(pma: *mut daac_pma, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
+                                   stream: *mut c_void, ranks: *const u32, n_ranks: usize, gap: i32, gap_id: u32, dev_ids: *mut *mut u32,
+                                   dev_spans: *mut *mut u64, dev_tok_offsets: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
