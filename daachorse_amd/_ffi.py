@@ -137,6 +137,18 @@ def lib():
     L.daac_tokenize_bpe.restype = C.c_int
     L.daac_tokenize_bpe_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, vp, sz, C.c_int, C.c_uint32, P(vp), P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
     L.daac_tokenize_bpe_batch.restype = C.c_int
+    L.daac_splitter_create.argtypes = [C.c_int, vp, sz, P(vp)]
+    L.daac_splitter_create.restype = C.c_int
+    L.daac_splitter_free.argtypes = [vp]
+    L.daac_splitter_free.restype = None
+    L.daac_split_batch.argtypes = [vp, u8p, vp, sz, C.c_int, vp, P(vp), P(vp), P(C.c_uint64)]
+    L.daac_split_batch.restype = C.c_int
+    L.daac_split.argtypes = [vp, u8p, sz, C.c_int, vp, P(vp), P(C.c_uint64)]
+    L.daac_split.restype = C.c_int
+    L.daac_offsets_compose.argtypes = [vp, vp, sz, vp, P(vp)]
+    L.daac_offsets_compose.restype = C.c_int
+    L.daac_spans_rebase.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]
+    L.daac_spans_rebase.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

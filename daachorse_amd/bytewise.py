@@ -49,6 +49,12 @@ class Gap(enum.IntEnum):
     Chars = 3   # one token per UTF-8 code point (a cut in front of every byte that is no continuation byte)
 
 
+class Split(enum.IntEnum):
+    """daac_split_rule: how split_batch cuts a document into words"""
+    Whitespace = 0   # \s+|\S+
+    Gpt2 = 1         # GPT-2's pre-tokenizer pattern
+
+
 class Match:
     """src/lib.rs:286-320"""
     __slots__ = ("_s", "_e", "_v")
@@ -725,6 +731,40 @@ class DoubleArrayAhoCorasick:
         out.append(DeviceOffsets(offs.value, b.n + 1))
         return self._token_result(out, k.value, device)
 
+    def tokenize_bpe_docs(self, docs, ranks=None, split=Split.Gpt2, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
+        """tokenize_bpe behind a pre-tokenizer split, per document: split_batch cuts the documents into words, tokenize_bpe_batch runs over
+        (hay, word_offsets) and daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or
+        (ids, spans, offsets) as tokenize_bpe_batch gives them, with document i's tokens in [offsets[i], offsets[i+1]) and spans that
+        count from the document's first byte.  `split`: a Split rule (the cached default splitter) or a Splitter.  Host documents are
+        uploaded once; a word above option bpe_doc_max answers 6."""
+        b = _Batch(docs)
+        if not b.is_device:
+            b = _Batch(_upload(b))
+        sp = split if isinstance(split, Splitter) else _default_splitter(split)
+        rk = self._ranks(ranks)
+        wo, dw = sp._run(b, stream)
+        ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        n_words = wo.count - 1
+        try:
+            _ffi.check(_ffi.lib().daac_tokenize_bpe_batch(self._h, int(engine), b.hay, wo.ptr, n_words, 1, stream, None if rk is None else rk.ctypes.data,
+                                                          0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(spn) if spans else None,
+                                                          C.byref(offs), C.byref(n), C.byref(k)))
+            out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+            if spans:
+                out.append(DeviceMatches(spn.value, n.value, SPAN_DTYPE))
+            word_tok = DeviceOffsets(offs.value, n_words + 1)
+            try:
+                if spans and n.value:
+                    _ffi.check(_ffi.lib().daac_spans_rebase(spn.value, word_tok.ptr, wo.ptr, dw.ptr, b.off, n_words, b.n, stream))
+                _ffi.check(_ffi.lib().daac_offsets_compose(word_tok.ptr, dw.ptr, b.n + 1, stream, C.byref(doc_offs)))
+            finally:
+                word_tok.free()
+        finally:
+            wo.free()
+            dw.free()
+        out.append(DeviceOffsets(doc_offs.value, b.n + 1))
+        return self._token_result(out, k.value, device)
+
     @staticmethod
     def _token_result(out, n_matches, device):
         out[0].n_matches = n_matches
@@ -801,6 +841,130 @@ def _device_u64(out, n):
     if not (hasattr(out, "data_ptr") and out.is_cuda and out.dtype.itemsize == 8 and out.is_contiguous() and out.numel() >= n):
         raise DaachorseError(1, "device results go to a contiguous CUDA tensor of n int64 / uint64 elements")
     return out.data_ptr()
+
+
+def _upload(b):
+    """a host _Batch as the device batch (uint8 CUDA tensor, int64 CUDA offsets tensor)"""
+    import torch
+    return torch.tensor(b.buf).cuda(), torch.from_numpy(b.offsets.astype(np.int64)).cuda()
+
+
+_WHITE_SPACE = (0x85, 0xA0, 0x1680) + tuple(range(0x2000, 0x200B)) + (0x2028, 0x2029, 0x202F, 0x205F, 0x3000)
+_char_classes = None
+
+
+def char_classes():
+    """The default classes of the code points from U+0080 on, as split_batch takes them: a uint32 array [R, 3] of sorted, disjoint ranges
+    {first, last, cls} with cls 1 = L (general categories L*), 2 = N (categories N*) and 3 = S (the non-ASCII White_Space code points:
+    U+0085, U+00A0, U+1680, U+2000..U+200A, U+2028, U+2029, U+202F, U+205F, U+3000); every other code point is O.  The categories are
+    the standard library's: Unicode `unicodedata.unidata_version` of the running Python.  Computed once and cached (read-only)."""
+    global _char_classes
+    if _char_classes is None:
+        import unicodedata
+        white = frozenset(_WHITE_SPACE)
+        rows, first, cur = [], 0, 0
+        for cp in range(0x80, 0x110001):
+            c = 0
+            if cp <= 0x10FFFF:
+                c = 3 if cp in white else {"L": 1, "N": 2}.get(unicodedata.category(chr(cp))[0], 0)
+            if c != cur:
+                if cur:
+                    rows.append((first, cp - 1, cur))
+                first, cur = cp, c
+        a = np.array(rows, dtype=np.uint32).reshape(len(rows), 3)
+        a.setflags(write=False)
+        _char_classes = a
+    return _char_classes
+
+
+class Splitter:
+    """daac_splitter: a split rule and the classes of the code points from U+0080 on (`classes`: rows {first, last, cls} as
+    char_classes() gives them, the default; sorted and disjoint, cls 1 = L, 2 = N, 3 = S).  Below U+0080 the classes are fixed."""
+
+    def __init__(self, rule=Split.Gpt2, classes=None):
+        self._h = None
+        a = char_classes() if classes is None else np.asarray(classes)
+        if a.size and (a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise DaachorseError(1, "classes must be rows {first, last, cls} of integers in 0 .. 0xFFFFFFFF")
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 3)
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().daac_splitter_create(int(rule), a.ctypes.data if a.size else None, a.shape[0], C.byref(h)))
+        self._h, self.rule = h.value, int(rule)
+
+    def _run(self, b, stream):
+        wo, dw, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        if not self._h:
+            raise DaachorseError(1, "the splitter has been freed")
+        _ffi.check(_ffi.lib().daac_split_batch(self._h, b.hay, b.off, b.n, b.is_device, stream, C.byref(wo), C.byref(dw), C.byref(n)))
+        return DeviceOffsets(wo.value, n.value + 1), DeviceOffsets(dw.value, b.n + 1)
+
+    def split_batch(self, docs, stream=None, device=False):
+        """-> (word_offsets, doc_words): word_offsets holds n_words + 1 positions in the batch's buffer (absolute: (hay, word_offsets) is a
+        batch itself; entry 0 is the first document's offset, the last entry the end of the last document), document i's words are
+        [doc_words[i], doc_words[i+1]); np.uint64 arrays, or DeviceOffsets (to_numpy / free) with device=True"""
+        return _offsets_result(self._run(_Batch(docs), stream), device)
+
+    def split(self, haystack, stream=None, device=False):
+        """-> word_offsets of one haystack: n_words + 1 positions, from 0 to its length"""
+        h = _Haystack(haystack)
+        if not self._h:
+            raise DaachorseError(1, "the splitter has been freed")
+        wo, n = C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_split(self._h, h.ptr, h.len, h.is_device, stream, C.byref(wo), C.byref(n)))
+        return _offsets_result([DeviceOffsets(wo.value, n.value + 1)], device)[0]
+
+    def free(self):
+        if self._h:
+            _ffi.lib().daac_splitter_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _offsets_result(dev, device):
+    if device:
+        return tuple(dev)
+    try:
+        return tuple(o.to_numpy() for o in dev)
+    finally:
+        for o in dev:
+            o.free()
+
+
+_default_splitters = {}
+
+
+def _default_splitter(rule):
+    rule = Split(rule) if rule in (0, 1) else rule
+    sp = _default_splitters.get(rule)
+    if sp is None:
+        sp = _default_splitters[rule] = Splitter(rule)
+    return sp
+
+
+def split_batch(docs, rule=Split.Gpt2, stream=None, device=False):
+    """Splitter(rule).split_batch(docs) on a cached splitter with the default classes (char_classes())"""
+    return _default_splitter(rule).split_batch(docs, stream=stream, device=device)
+
+
+def offsets_compose(inner, outer, stream=None, device=False):
+    """daac_offsets_compose: inner[outer] of two device arrays of 8-byte offsets (DeviceOffsets, or contiguous int64 / uint64 CUDA
+    tensors) -> np.uint64[len(outer)], or DeviceOffsets with device=True"""
+    def arg(x):
+        if isinstance(x, DeviceOffsets):
+            return x.ptr, x.count
+        if not (hasattr(x, "data_ptr") and x.is_cuda and x.dtype.itemsize == 8 and x.is_contiguous() and x.dim() == 1):
+            raise DaachorseError(1, "offsets_compose takes DeviceOffsets or contiguous one-dimensional CUDA tensors of int64 / uint64")
+        return x.data_ptr(), x.numel()
+
+    (p_in, _), (p_out, n) = arg(inner), arg(outer)
+    out = C.c_void_p()
+    _ffi.check(_ffi.lib().daac_offsets_compose(p_in, p_out, n, stream, C.byref(out)))
+    return _offsets_result([DeviceOffsets(out.value, n)], device)[0]
 
 
 def scan_count_multi(pma, mode, shards, engine=Engine.Auto, checksum=True):

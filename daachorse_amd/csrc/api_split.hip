@@ -1,0 +1,282 @@
+// C ABI (include/daachorse_amd.h), part 12: the pre-tokenizer split of a text or a batch into words on the device (daac_splitter_create,
+// daac_split_batch, daac_split) and the gather that turns offsets over words into offsets over documents (daac_offsets_compose).  No
+// automaton is involved: a splitter is a rule and a class table.  This file validates, builds the two-stage class table on the host,
+// uploads it per device on first use, stages a host text once, marks the document starts, runs the flag pass, sums the tile counts (one
+// read-back), allocates the result and runs the write passes; the kernels are split_kernels.hip.  A single haystack is a batch of one
+// document.
+#include "api_internal.hpp"
+#include "batch.hpp"
+#include "split.hpp"
+
+struct daac_splitter {
+    int rule = DAAC_SPLIT_GPT2;
+    std::vector<uint16_t> stage1;   // kSplitStage1 block numbers
+    std::vector<uint8_t> stage2;    // blocks of kSplitBlockBytes; block 0 is all O
+    std::mutex mu;
+    std::map<int, void *> dev;      // per device: stage1, then stage2 at byte 2 * kSplitStage1
+};
+
+namespace {
+
+constexpr unsigned long long kNoDoc = ~0ull;
+
+daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    std::lock_guard<std::mutex> g(sp->mu);
+    auto it = sp->dev.find(device);
+    if (it == sp->dev.end()) {
+        void *d = nullptr;
+        const size_t b1 = sp->stage1.size() * sizeof(uint16_t);
+        HIP_TRY(hipMalloc(&d, b1 + sp->stage2.size()));
+        std::unique_ptr<void, void (*)(void *)> guard(d, [](void *p) { (void)hipFree(p); });
+        HIP_TRY(hipMemcpy(d, sp->stage1.data(), b1, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(d) + b1, sp->stage2.data(), sp->stage2.size(), hipMemcpyHostToDevice));
+        it = sp->dev.emplace(device, guard.release()).first;
+    }
+    out.stage1 = static_cast<const uint16_t *>(it->second);
+    out.stage2 = static_cast<const uint8_t *>(it->second) + sp->stage1.size() * sizeof(uint16_t);
+    return DAAC_OK;
+}
+
+const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : "whitespace"; }
+
+// Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
+daac_status split_precheck(const daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, bool outs_ok) {
+    if (!sp || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    return DAAC_OK;
+}
+
+daac_status too_many_words(uint64_t words) {
+    set_error("the list of " + std::to_string(words) + " words exceeds max_result_bytes");
+    return DAAC_ERR_AUTOMATON_SCALE;
+}
+
+// `text`: the byte at offsets[0] on the device; `d_off`: the n + 1 offsets on the device (n >= 1, checked); ends = {offsets[0], offsets[n]}.
+daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t ends[2], const unsigned long long *d_off, uint64_t n, hipStream_t stream,
+                         uint64_t **dev_word_offsets, uint64_t **dev_doc_words, uint64_t *n_words) {
+    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
+    const uint64_t total = ends[1] - ends[0];
+    if (n + 1 > static_cast<uint64_t>(OPT(max_result_bytes)) / sizeof(uint64_t)) { set_error("doc_words of " + std::to_string(n) + " documents exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
+    void *doc_words = nullptr;
+    HIP_TRY(dev_malloc(&doc_words, (n + 1) * sizeof(uint64_t), stream));
+    auto g_docs = guard(doc_words);
+    if (total == 0) {   // documents, all of them empty: no word
+        void *wo = nullptr;
+        HIP_TRY(dev_malloc(&wo, sizeof(uint64_t), stream));
+        auto g_wo = guard(wo);
+        HIP_TRY(hipMemsetAsync(doc_words, 0, (n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(wo, &ends[0], sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        g_last_kernel = std::string("split rule=") + rule_name(sp->rule) + " docs=" + std::to_string(n) + " bytes=0 words=0";
+        *dev_word_offsets = static_cast<uint64_t *>(g_wo.release());
+        *dev_doc_words = static_cast<uint64_t *>(g_docs.release());
+        *n_words = 0;
+        return DAAC_OK;
+    }
+    daac::SplitArgs a{};
+    daac_status st = table_of(sp, a.tab);
+    if (st != DAAC_OK) return st;
+    a.text = text;
+    a.total = total;
+    a.base = ends[0];
+    a.doc_off = d_off;
+    a.n_docs = n;
+    a.rule = sp->rule;
+    a.tiles = (total + daac::kSplitTile - 1) / daac::kSplitTile;
+    // the scratch: the tile counts, their sum, the sum's scratch, the masks, the marks
+    const uint64_t n_mask = a.tiles * (daac::kSplitTile / 64), n_mark = a.tiles * (daac::kSplitTile / 32) + 1, n_scan = exclusive_scan_scratch(a.tiles);
+    DevBuf work;
+    HIP_TRY(work.alloc((a.tiles + 1 + n_scan + n_mask) * sizeof(unsigned long long) + n_mark * sizeof(uint32_t), stream));
+    a.counts = static_cast<unsigned long long *>(work.p);
+    unsigned long long *sum = a.counts + a.tiles, *scan_scratch = sum + 1;
+    a.n_words = sum;
+    a.masks = scan_scratch + n_scan;
+    a.marks = reinterpret_cast<uint32_t *>(a.masks + n_mask);
+    HIP_TRY(hipMemsetAsync(a.marks, 0, n_mark * sizeof(uint32_t), stream));
+    HIP_TRY(daac::launch_split_marks(a, stream));
+    HIP_TRY(daac::launch_split_flags(a, stream));
+    HIP_TRY(daac::launch_exclusive_scan(a.counts, a.tiles, sum, scan_scratch, stream));
+    unsigned long long words = 0;
+    HIP_TRY(hipMemcpyAsync(&words, sum, sizeof(words), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (words > total) { set_error("the word count does not fit the text"); return DAAC_ERR_DEVICE; }   // (never seen: a word has a byte)
+    if (words + 1 > static_cast<uint64_t>(OPT(max_result_bytes)) / sizeof(uint64_t)) return too_many_words(words);
+    void *wo = nullptr;
+    HIP_TRY(dev_malloc(&wo, (words + 1) * sizeof(uint64_t), stream));
+    auto g_wo = guard(wo);
+    a.word_offsets = static_cast<unsigned long long *>(wo);
+    a.doc_words = static_cast<unsigned long long *>(doc_words);
+    HIP_TRY(daac::launch_split_scatter(a, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
+    g_last_kernel = std::string("split rule=") + rule_name(sp->rule) + " docs=" + std::to_string(n) + " bytes=" + std::to_string(total) + " words=" + std::to_string(words) +
+                    " tile=" + std::to_string(daac::kSplitTile);
+    *dev_word_offsets = static_cast<uint64_t *>(g_wo.release());
+    *dev_doc_words = static_cast<uint64_t *>(g_docs.release());
+    *n_words = words;
+    return DAAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out) {
+    if (!out) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2) { set_error("rule is neither DAAC_SPLIT_WHITESPACE nor DAAC_SPLIT_GPT2"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n_ranges && !ranges) { set_error("ranges is NULL with n_ranges = " + std::to_string(n_ranges)); return DAAC_ERR_INVALID_ARGUMENT; }
+    for (size_t i = 0; i < n_ranges; ++i) {
+        const daac_char_range &r = ranges[i];
+        const std::string at = "range " + std::to_string(i);
+        if (r.last < r.first) { set_error(at + ": last < first"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (r.first < 0x80u) { set_error(at + ": first is below U+0080 (the ASCII classes are fixed)"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (r.last > 0x10FFFFu) { set_error(at + ": last is above U+10FFFF"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (r.cls < 1u || r.cls > 3u) { set_error(at + ": cls is not 1 (L), 2 (N) or 3 (S)"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (i && r.first <= ranges[i - 1].last) { set_error(at + ": the ranges are not sorted and disjoint"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    // the two-stage table: equal blocks of 256 code points are stored once
+    std::unique_ptr<daac_splitter> sp(new daac_splitter);
+    sp->rule = rule;
+    sp->stage1.assign(daac::kSplitStage1, 0);
+    sp->stage2.assign(daac::kSplitBlockBytes, 0);
+    std::map<std::vector<uint8_t>, uint16_t> seen;
+    seen.emplace(sp->stage2, 0);
+    size_t r = 0;
+    for (uint32_t hi = 0; hi < daac::kSplitStage1; ++hi) {
+        const uint32_t lo_cp = hi << 8, hi_cp = lo_cp + 255u;
+        while (r < n_ranges && ranges[r].last < lo_cp) ++r;
+        if (r == n_ranges || ranges[r].first > hi_cp) continue;   // all O: block 0
+        std::vector<uint8_t> blk(daac::kSplitBlockBytes, 0);
+        for (size_t j = r; j < n_ranges && ranges[j].first <= hi_cp; ++j)
+            for (uint32_t cp = std::max(ranges[j].first, lo_cp); cp <= std::min(ranges[j].last, hi_cp); ++cp)
+                blk[(cp & 255u) >> 2] = static_cast<uint8_t>(blk[(cp & 255u) >> 2] | ranges[j].cls << (2u * (cp & 3u)));
+        auto it = seen.find(blk);
+        if (it == seen.end()) {
+            it = seen.emplace(blk, static_cast<uint16_t>(seen.size())).first;   // (at most kSplitStage1 blocks: 16 bits hold the number)
+            sp->stage2.insert(sp->stage2.end(), blk.begin(), blk.end());
+        }
+        sp->stage1[hi] = it->second;
+    }
+    *out = sp.release();
+    return DAAC_OK;
+}
+
+void daac_splitter_free(daac_splitter *sp) {
+    if (!sp) return;
+    for (auto &kv : sp->dev) (void)hipFree(kv.second);
+    delete sp;
+}
+
+daac_status daac_split_batch(daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
+                             uint64_t **dev_word_offsets, uint64_t **dev_doc_words, uint64_t *n_words) {
+    PmaScope scope_(nullptr);   // no handle: the process-wide options
+    daac_status st = split_precheck(sp, hay, offsets, n, hay_is_device, dev_word_offsets && dev_doc_words && n_words);
+    if (st != DAAC_OK) return st;
+    *dev_word_offsets = nullptr;
+    *dev_doc_words = nullptr;
+    *n_words = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) {   // no document: one word offset and one doc_words entry, both 0
+        void *wo = nullptr, *dw = nullptr;
+        HIP_TRY(dev_malloc(&wo, sizeof(uint64_t), stream));
+        std::unique_ptr<void, std::function<void(void *)>> g_wo(wo, [stream](void *q) { dev_free(q, stream); });
+        HIP_TRY(dev_malloc(&dw, sizeof(uint64_t), stream));
+        std::unique_ptr<void, std::function<void(void *)>> g_dw(dw, [stream](void *q) { dev_free(q, stream); });
+        HIP_TRY(hipMemsetAsync(wo, 0, sizeof(uint64_t), stream));
+        HIP_TRY(hipMemsetAsync(dw, 0, sizeof(uint64_t), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        g_last_kernel = std::string("split rule=") + rule_name(sp->rule) + " docs=0 bytes=0 words=0";
+        *dev_word_offsets = static_cast<uint64_t *>(g_wo.release());
+        *dev_doc_words = static_cast<uint64_t *>(g_dw.release());
+        return DAAC_OK;
+    }
+    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
+    void *staged = nullptr;
+    const uint8_t *dev_hay = hay;
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
+    DevBuf off_buf;
+    if (!hay_is_device) {   // the text and its offsets go to the device once
+        ends[0] = offsets[0];
+        ends[1] = offsets[n];
+        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    if (!hay_is_device) {
+        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        d_off = static_cast<const unsigned long long *>(off_buf.p);
+    } else {   // daac_scan_count_batch's validation of device offsets: the first decreasing pair, read back with the two ends
+        HIP_TRY(off_buf.alloc(3 * sizeof(unsigned long long), stream));
+        unsigned long long *flags = static_cast<unsigned long long *>(off_buf.p);
+        HIP_TRY(hipMemsetAsync(flags, 0xff, sizeof(unsigned long long), stream));
+        HIP_TRY(daac::launch_batch_plan(d_off, n, 1, nullptr, flags, stream));
+        HIP_TRY(hipMemcpyAsync(flags + 1, d_off, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(flags + 2, d_off + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        unsigned long long h[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (h[0] != kNoDoc) { set_error("offsets decrease at document " + std::to_string(h[0])); return DAAC_ERR_INVALID_ARGUMENT; }
+        ends[0] = h[1];
+        ends[1] = h[2];
+    }
+    return split_device(sp, dev_hay + ends[0], ends, d_off, n, stream, dev_word_offsets, dev_doc_words, n_words);
+}
+
+daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, uint64_t **dev_word_offsets, uint64_t *n_words) {
+    if (!sp || !dev_word_offsets || !n_words) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_word_offsets = nullptr;
+    *n_words = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const uint64_t one_doc[2] = {0, len};
+    if (!hay_is_device) {   // host offsets with the host text
+        uint64_t *doc_words = nullptr;
+        const uint8_t none = 0;
+        const daac_status st = daac_split_batch(sp, hay ? hay : &none, one_doc, 1, 0, stream_, dev_word_offsets, &doc_words, n_words);
+        dev_free(doc_words, stream);
+        return st;
+    }
+    PmaScope scope_(nullptr);
+    DevBuf off_buf;
+    HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
+    HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+    uint64_t *doc_words = nullptr;
+    const daac_status st = split_device(sp, hay, one_doc, static_cast<const unsigned long long *>(off_buf.p), 1, stream, dev_word_offsets, &doc_words, n_words);
+    dev_free(doc_words, stream);
+    return st;
+}
+
+daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_outer, size_t n_outer, void *stream_, uint64_t **dev_out) {
+    if (!dev_out || (n_outer && (!dev_inner || !dev_outer))) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_out = nullptr;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    void *out = nullptr;
+    HIP_TRY(dev_malloc(&out, n_outer * sizeof(uint64_t), stream));
+    std::unique_ptr<void, std::function<void(void *)>> g(out, [stream](void *q) { dev_free(q, stream); });
+    HIP_TRY(daac::launch_offsets_compose(reinterpret_cast<const unsigned long long *>(dev_inner), reinterpret_cast<const unsigned long long *>(dev_outer), n_outer,
+                                         static_cast<unsigned long long *>(out), stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *dev_out = static_cast<uint64_t *>(g.release());
+    return DAAC_OK;
+}
+
+daac_status daac_spans_rebase(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_word_offsets, const uint64_t *dev_doc_words,
+                              const uint64_t *dev_doc_offsets, size_t n_words, size_t n_docs, void *stream_) {
+    if (n_words && n_docs && (!dev_spans || !dev_tok_offsets || !dev_word_offsets || !dev_doc_words || !dev_doc_offsets)) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(daac::launch_spans_rebase(reinterpret_cast<unsigned long long *>(dev_spans), reinterpret_cast<const unsigned long long *>(dev_tok_offsets),
+                                      reinterpret_cast<const unsigned long long *>(dev_word_offsets), reinterpret_cast<const unsigned long long *>(dev_doc_words),
+                                      reinterpret_cast<const unsigned long long *>(dev_doc_offsets), n_words, n_docs, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DAAC_OK;
+}
+
+}  // extern "C"

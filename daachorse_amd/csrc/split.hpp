@@ -1,0 +1,68 @@
+// split_batch on the device (daac_split_batch, daac_split, daac_offsets_compose): what api_split.hip and split_kernels.hip share.
+//
+// The definition (include/daachorse_amd.h has it in full).  A document is cut into units: a well-formed UTF-8 sequence (Unicode
+// Table 3-7) that lies wholly inside the document is one unit of its code point's class, every other byte a unit of class O.  The
+// classes are L, N, S and O; below U+0080 they are fixed, from U+0080 on they come from the splitter's ranges.  The words of a
+// document are the successive matches of \s+|\S+ (DAAC_SPLIT_WHITESPACE) or of GPT-2's pattern (DAAC_SPLIT_GPT2) over the units:
+// contiguous, covering the document.  Whether a word starts at a byte is decided from the bytes of its document at most kSplitBack
+// before it and kSplitAhead - 1 after it (split_kernels.hip has the local form), so the unit of parallelism is the byte.
+//
+// Positions p count from offsets[0]: 0 <= p < total = offsets[n] - offsets[0].  The scratch of a call:
+//   marks   one bit per position 0 .. total: a non-empty document starts here (bit `total`: the text ends here); set with atomicOr
+//   masks   one bit per position, kSplitTile / 64 words of 64 per tile: a word starts here
+//   counts  per tile: the set bits of its masks; their exclusive sum ranks the word starts
+#pragma once
+
+#include <cstdint>
+
+#ifndef DAAC_SPLIT_HOST
+#include <hip/hip_runtime.h>
+#endif
+
+namespace daac {
+
+constexpr uint32_t kSplitLanes = 256;    // lanes of a workgroup
+constexpr uint32_t kSplitTile = 1024;    // positions of a workgroup: kSplitTile / kSplitLanes per lane, one ballot each
+constexpr int kSplitBack = 12;           // bytes in front of a position its decision may read: three units of four bytes
+constexpr int kSplitAhead = 8;           // bytes from a position on its decision may read: the position and seven more
+constexpr uint32_t kSplitStage1 = 0x1100;   // entries of the class table's first stage: one per 256 code points up to U+10FFFF
+constexpr uint32_t kSplitBlockBytes = 64;   // a second-stage block: 256 code points, two bits each
+
+enum : uint32_t { kSplitO = 0, kSplitL = 1, kSplitN = 2, kSplitS = 3 };
+
+// The class of a code point from U+0080 on: (stage2[stage1[cp >> 8] * 64 + ((cp & 255) >> 2)] >> 2 * (cp & 3)) & 3.  Block 0 is all O.
+struct SplitTable {
+    const uint16_t *stage1;   // kSplitStage1 block numbers
+    const uint8_t *stage2;    // blocks of kSplitBlockBytes
+};
+
+struct SplitArgs {
+    const uint8_t *text;                  // the byte at position 0 (offsets[0] of the caller's buffer), any alignment
+    uint64_t total;                       // positions
+    uint64_t base;                        // offsets[0]: what a position is counted from
+    const unsigned long long *doc_off;    // n_docs + 1 offsets
+    uint64_t n_docs;
+    int rule;
+    SplitTable tab;
+    uint32_t *marks;                      // tiles * kSplitTile / 32 + 1 words
+    unsigned long long *masks;            // tiles * kSplitTile / 64 words
+    unsigned long long *counts;           // tiles: the flag pass's counts, then their exclusive sum
+    const unsigned long long *n_words;    // 1: the sum of the counts
+    uint64_t tiles;
+    // the write passes
+    unsigned long long *word_offsets;     // n_words + 1
+    unsigned long long *doc_words;        // n_docs + 1
+};
+
+#ifndef DAAC_SPLIT_HOST
+hipError_t launch_split_marks(const SplitArgs &a, hipStream_t stream);     // marks (zeroed by the caller)
+hipError_t launch_split_flags(const SplitArgs &a, hipStream_t stream);     // masks and counts
+hipError_t launch_split_scatter(const SplitArgs &a, hipStream_t stream);   // word_offsets and doc_words, the closing entries included
+// out[i] = inner[outer[i]] for i < n
+hipError_t launch_offsets_compose(const unsigned long long *inner, const unsigned long long *outer, uint64_t n, unsigned long long *out, hipStream_t stream);
+// spans of a word batch's tokens, relative to the word, made relative to the word's document: one lane per word
+hipError_t launch_spans_rebase(unsigned long long *spans, const unsigned long long *tok_offsets, const unsigned long long *word_offsets,
+                               const unsigned long long *doc_words, const unsigned long long *doc_off, uint64_t n_words, uint64_t n_docs, hipStream_t stream);
+#endif
+
+}  // namespace daac

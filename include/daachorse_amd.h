@@ -52,7 +52,9 @@ extern "C" {
  *   (6, likewise: daac_tokenize_unigram / daac_tokenize_unigram_batch — the segmentation whose pieces' scores sum highest, a Viterbi pass
  *      over the tuple list of an overlapping scan, on the device.)
  *   (6, likewise: daac_tokenize_bpe / daac_tokenize_bpe_batch — the token ids of byte-pair merging in rank order over the same tuple
- *      list, on the device — and the option bpe_doc_max.) */
+ *      list, on the device — and the option bpe_doc_max.)
+ *   (6, likewise: daac_splitter_create / daac_split_batch / daac_split, daac_offsets_compose and daac_spans_rebase — the pre-tokenizer
+ *      split of a batch into words, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -561,6 +563,58 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
                                     void *stream, const uint32_t *ranks, size_t n_ranks, int gap, uint32_t gap_id,
                                     uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets,
                                     uint64_t *n_tokens, uint64_t *n_matches);
+
+/* ---- split_batch: the pre-tokenizer split of a batch into words --------------------------------------------------------------------------
+ * What stands in front of the three tokenizers above on real text: every document is cut into words, and (hay, word_offsets) is itself
+ * a batch that every *_batch call accepts.  No automaton is involved: a splitter is a rule and a table of character classes.
+ *   Units: a document is any bytes.  It is cut into units by the well-formed UTF-8 table (Unicode Table 3-7: lead bytes C2..F4 only;
+ *     E0 / ED / F0 / F4 restrict their second byte; no overlong forms, no surrogates, nothing above U+10FFFF).  A well-formed sequence
+ *     that lies wholly inside the document is one unit, and its class is the class of its code point.  Every other byte is a unit of its
+ *     own, of class O.  Documents are independent: a sequence cut by a document's end is malformed, and no look-back or look-ahead
+ *     leaves the document.
+ *   Classes: L (letter), N (number), S (whitespace) and O (everything else).  Below U+0080 they are fixed: A-Z a-z are L, 0-9 are N,
+ *     0x09..0x0D and 0x20 are S, the rest is O.  From U+0080 on they come from the splitter's table of sorted, disjoint ranges
+ *     {first, last, cls}, cls in {1 = L, 2 = N, 3 = S}; a code point in no range is O.
+ *   Rules: both partition each document — its words are contiguous and cover it, nothing is dropped.
+ *     DAAC_SPLIT_WHITESPACE: the words are the matches of \s+|\S+: maximal runs of S units and maximal runs of other units.
+ *     DAAC_SPLIT_GPT2: the words are the successive matches of
+ *       's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ *     with \p{L} = L, \p{N} = N and \s = S, case-sensitive: the sequential scanner that tries the alternatives in order at each
+ *     position, greedy, the fifth alternative backtracking.  (GPT-2, RoBERTa, BART and every byte-level BPE vocabulary trained with it.)
+ *   The kernels evaluate an equivalent local form — whether a word starts at a unit follows from three units in front of it and one
+ *     behind it (split_kernels.hip states it) — so the unit of parallelism is the byte.  A word start is always the first byte of a unit.
+ * daac_splitter_create builds a two-stage class table on the host from the ranges (n_ranges = 0: every code point from U+0080 on is O);
+ * the table is uploaded per device on first use.  Status 1: a NULL out, an unknown rule, ranges that are unsorted, overlapping, have
+ * last < first, first < 0x80, last > 0x10FFFF or cls outside 1..3.
+ * daac_split_batch: *dev_word_offsets holds *n_words + 1 u64 positions in hay — absolute, entry 0 is offsets[0], the last entry is
+ * offsets[n]; *dev_doc_words holds n + 1 u64: document i's words are [doc_words[i], doc_words[i+1]), an empty document has none,
+ * doc_words[n] == n_words.  Both are device memory, released with daac_device_free.  The call returns after the stream has finished.
+ * n = 0: one word offset and one doc_words entry, both 0, and *n_words = 0.  No byte outside [offsets[0], offsets[n]) is read.
+ * Decided before a device is touched — status 1: a NULL sp, dev_word_offsets, dev_doc_words or n_words; the batch offset rules of
+ * daac_scan_count_batch (host offsets; device offsets are validated as that call validates them, with one read-back).  Status 2: a
+ * word list above the process-wide option max_result_bytes (8 bytes a word), answered before it is allocated.  A host haystack is
+ * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=..".
+ * Method: one lane per document marks its first byte in a bit array; a workgroup stages a tile of 1024 bytes, 12 in front and 7 behind
+ * in LDS and each lane decides its byte; a wave ballot makes a 64-bit mask word; the per-tile popcounts are summed (one read-back of
+ * the total) and a second pass writes every start at its rank.  Integer work only: the result is a function of the input alone. */
+typedef enum { DAAC_SPLIT_WHITESPACE = 0, DAAC_SPLIT_GPT2 = 1 } daac_split_rule;
+typedef struct { uint32_t first, last, cls; } daac_char_range;
+typedef struct daac_splitter daac_splitter;
+daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out);
+void daac_splitter_free(daac_splitter *sp);
+daac_status daac_split_batch(daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream,
+                             uint64_t **dev_word_offsets, uint64_t **dev_doc_words, uint64_t *n_words);
+/* A single haystack: a batch of one document {0, len}. */
+daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                       uint64_t **dev_word_offsets, uint64_t *n_words);
+/* out[i] = inner[outer[i]] for i < n_outer, all three in device memory (*dev_out: daac_device_free).  With inner = the token offsets of
+ * the word batch and outer = doc_words (n + 1 entries) it gives the token offsets per document.  Status 1: a NULL argument. */
+daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_outer, size_t n_outer, void *stream, uint64_t **dev_out);
+/* The spans of a word batch's tokens ({start, end} relative to the token's word, in place) made relative to the word's document:
+ * tok_offsets (n_words + 1) are the word batch's token offsets, word_offsets and doc_words daac_split_batch's, doc_offsets (n_docs + 1)
+ * the offsets that call was given.  One lane per word.  Returns after the stream has finished. */
+daac_status daac_spans_rebase(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_word_offsets, const uint64_t *dev_doc_words,
+                              const uint64_t *dev_doc_offsets, size_t n_words, size_t n_docs, void *stream);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
