@@ -41,6 +41,12 @@
 // displacement table (one byte a bucket) lies in LDS where the coarse directory lay, the records in slot order in dhit_h.  10 VALU and one ds_read_u8
 // a batch of 64 survivors instead of 23 and four LDS reads; the TAIL body, the plain body and the density probe keep ranks.  A handle whose dictionary
 // is too dense for a table that small keeps the rank path (build_gram4_mph says no).  profiles/r10_gram4_*.txt.
+// Round 11: (a) a slab entry of the plain and FILT bodies is {record x, record y, position, text}: the gathered pair is stored from the registers
+// it was loaded into — with the position first the compiler moved it one register up right behind the gather, and waited for it there.  (b) K = 3:
+// the M-word address of an odd position from the even position's intermediate (gram4_index.hpp): five instructions a pair, not six.  (c) hit-list
+// entries are LDS addresses of byte p - 3 (`derive` adds no base and subtracts no 3).  (d) the count sum is v_and_b32 and two v_bcnt_u32_b32 onto the
+// region's count.  (e) the probe's pass mask is the two compares' masks or-ed on the scalar unit.  SQ_INSTS_VALU 18.51 -> 17.36 per byte and lane
+// (profiles/r11_gram4_*.txt).
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -50,13 +56,14 @@
 
 #include "device_tables.hpp"
 #include "gram4_filter.hpp"
+#include "gram4_index.hpp"
 
 namespace daac {
 
 namespace {
 
 typedef uint32_t g4_u32x4_t __attribute__((ext_vector_type(4)));
-constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the hit byte's offset in the wave's text slot
+constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the LDS address of the byte three before the hit byte
 constexpr uint32_t kProbePercent4 = 3;  // density probe: TAIL when more than 3 % of the sampled positions start a walker
 typedef __attribute__((address_space(3))) const uint32_t lds4_cu32;
 typedef __attribute__((address_space(3))) uint32_t lds4_u32;
@@ -159,14 +166,17 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                                                         // offset beside a scalar base in the load, not a 64-bit add per chunk)
     const uint32_t wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t C4 = C * 4u, CC4 = C * C * 4u;
+    const uint32_t offM1 = g4i_off1(offM, C);   // the second constant of an odd position's M-word address (gram4_index.hpp)
     const uint32_t ub4 = g.unused_byte * 0x01010101u;
     const uint8_t *__restrict__ hay = a.hay_al;
     const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
     // per-wave LDS: the text slot; the hit lists of all waves come first
     const uint32_t tb = L.off_wave + wave_in_wg * L.wave_stride;   // wave-uniform
     const uint32_t listb = wave_in_wg * (kList4 * 2u);
-    // this wave's slab of pending walkers, 16-byte entries.  plain: {position of the hit byte, hit record x, hit record y, the four text
-    // bytes behind the hit}; TAIL: {position, state | class << 27, text bytes from position + 2 on, three more | how many << 24}
+    // this wave's slab of pending walkers, 16-byte entries.  plain: {hit record x, hit record y, position of the hit byte, the four text
+    // bytes behind the hit} — the gathered pair first: it is stored from the registers it was loaded into, so nothing has to wait for it
+    // where it was asked for (round 11) —; TAIL and what the drain writes back: {position, state | class << 27, text bytes from
+    // position + 2 on, three more | how many << 24}
     const uint64_t slab_index = (static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave_in_wg) * a.wq_slab;
     uint4 *__restrict__ slab4 = reinterpret_cast<uint4 *>(a.wq) + slab_index;
     // Positions in the queues, the pending stages and the slab are 32-bit offsets from `epoch_base`, a multiple of 2 GiB: a region (a power
@@ -222,7 +232,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     auto drain = [&]() {
         const uint4 *__restrict__ recs = TAIL ? g.drec_t : g.drec_c;
         uint32_t n_in = wq_n;
-        bool raw = !TAIL;   // plain: the first pass reads what the batches left: {position, hit record x, hit record y, four text bytes}
+        bool raw = !TAIL;   // plain: the first pass reads what the batches left: {hit record x, hit record y, position, four text bytes}
         while (n_in != 0) {
             uint32_t n_out = 0;
             for (uint32_t base = 0; base < n_in; base += 64u) {
@@ -230,11 +240,12 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 const bool live = i < n_in;
                 uint4 e = uint4{0u, 0u, 0u, 0u};
                 if (live) e = slab4[i];
-                uint32_t state, n_ahead;
+                uint32_t state, n_ahead, pos = e.x;
                 unsigned long long ah;
                 if (raw) {
                     const uint32_t k1 = cls_of(e.w & 0xffu);
-                    state = e.z + __popc(e.y & below(k1));
+                    state = e.y + __popc(e.x & below(k1));
+                    pos = e.z;
                     ah = e.w >> 8;
                     n_ahead = 3;
                 } else {
@@ -244,7 +255,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 }
                 uint4 rr = uint4{0u, 0u, 0u, 0u};
                 if (live) rr = recs[state];  // {cmap, first_child, own_cnt, -} or a tail record
-                const uint64_t vn = epoch_base + e.x + 2;  // the state consumed the byte before vn
+                const uint64_t vn = epoch_base + pos + 2;  // the state consumed the byte before vn
                 bool cont = false;
                 uint32_t next_state = 0;
                 if (rr.x >> 31) {   // the rest is one path (idle lanes: a zero record, nothing happens)
@@ -262,7 +273,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                     if (cont) {
                         const uint32_t at = n_out + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0));
                         ah >>= 8;
-                        slab4[at] = uint4{e.x + 1u, next_state, static_cast<uint32_t>(ah), static_cast<uint32_t>(ah >> 32) | ((n_ahead - 1u) << 24)};
+                        slab4[at] = uint4{pos + 1u, next_state, static_cast<uint32_t>(ah), static_cast<uint32_t>(ah >> 32) | ((n_ahead - 1u) << 24)};
                     }
                     n_out += static_cast<uint32_t>(__popcll(m));
                 }
@@ -273,9 +284,10 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         wq_n = 0;
     };
 
-    // ---- the hit list: entry = offset of the hit byte from the start of the wave's text slot (u16)
+    // ---- the hit list: entry = LDS address of byte p - 3 of the hit byte p in the wave's text slot (u16: the lists and slots end below 64 KB;
+    // round 11 — an offset from the slot's start cost `derive` an add of the slot's base and a subtract of 3 in every batch)
     uint32_t q_head = 0, q_tail = 0;   // wave-uniform: entries [q_head, q_tail) of the list are queued, not yet taken
-    uint32_t posbias = 0;              // (virtual position of a byte - epoch_base) - (its LDS address), of the text in the slot
+    uint32_t posbias = 0;              // (virtual position of a hit byte - epoch_base) - (its list entry), of the text in the slot
     uint32_t st_n = 0;                 // wave-uniform: lanes [0, st_n) hold an entry of the NEXT batch already taken out of queue and slot
     uint32_t pend_lo = 0;              // the bytes p-3 .. p of the next batch's entry (p = its hit byte); pend_pos / pend_t0 / pend_t1 go with it
     uint4 pend = uint4{0u, 0u, 0u, 0u};  // record read for the previous batch, not yet consumed; zero for idle lanes
@@ -339,14 +351,14 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         if (FILT) {
             const uint32_t k1 = cls_of(fp_t0 & 0xffu);
             cnt32 += (r.x >> kGram4EndsBitDev) & 1u;
-            push_walker(__builtin_amdgcn_ubfe(r.x, k1, 1) != 0, uint4{fp_pos, r.x, r.y, fp_t0});
+            push_walker(__builtin_amdgcn_ubfe(r.x, k1, 1) != 0, uint4{r.x, r.y, fp_pos, fp_t0});
             return;
         }
         const uint32_t k1 = cls_of(pend_t0 & 0xffu);
         if (!TAIL) {
             cnt32 += (r.x >> kGram4EndsBitDev) & 1u;
             // (the first child of a branch that goes on is worked out in the drain, 64 branches wide: here three or four lanes of 64 go on)
-            push_walker(__builtin_amdgcn_ubfe(r.x, k1, 1) != 0, uint4{pend_pos, r.x, r.y, pend_t0});
+            push_walker(__builtin_amdgcn_ubfe(r.x, k1, 1) != 0, uint4{r.x, r.y, pend_pos, pend_t0});
             return;
         }
         bool go;
@@ -374,9 +386,8 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     // four (TAIL: eight) behind it.  After this the entries no longer refer to the slot.
     auto derive = [&](uint32_t first, uint32_t cnt) {
         if (lane - first < cnt) {
-            const uint32_t e = tb + *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(listb + ((q_head + lane - first) << 1)));
-            pend_pos = e + posbias;
-            const uint32_t t3 = e - 3u;
+            const uint32_t t3 = *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(listb + ((q_head + lane - first) << 1)));
+            pend_pos = t3 + posbias;
             const uint32_t a0 = t3 & ~3u, sh = t3 & 3u;
             // the dwords around the hit byte (the slot is self-contained: never outside [slot + 12, slot + SLOT)).  (Round 8 tried two
             // ds_read_b32 at the byte address instead: 7x slower than these reads on gfx950, tools/micro/lds_unaligned.hip)
@@ -466,8 +477,10 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             // first stage: the probe of gram4_filter.hpp on the raw bytes p-K .. p and p + 1 — one word, the GO key's two bits or the ENDS key's four
             const G4Probe pr = g4f_probe(K == 3 ? pend_lo : pend_lo >> 8, pend_t0 & 0xffu, bloomW);
             const uint32_t fw = lds_u32(offB + (pr.word << 2));
-            const bool pass = lane < n && ((pr.go & ~fw) == 0u || (pr.ends & ~fw) == 0u);
-            const unsigned long long pm = __builtin_amdgcn_ballot_w64(pass);
+            // (the two compares' masks or-ed and cut to the batch's lanes on the scalar unit: as one bool the compiler rebuilt the ballot
+            // from a v_cndmask_b32 and a third compare — round 11)
+            const unsigned long long in_batch = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+            const unsigned long long pm = (__builtin_amdgcn_ballot_w64((pr.go & ~fw) == 0u) | __builtin_amdgcn_ballot_w64((pr.ends & ~fw) == 0u)) & in_batch;
             if (pm != 0) {
                 // survivors move to lanes sb_n, sb_n + 1, .. (mod 64) — one forward permute per word; the others all go to lane sb_n - 1 (mod 64),
                 // which is outside [sb_n, sb_n + s) unless all 64 pass, and whose value is not looked at (round 8: before, they filled the lanes in
@@ -563,7 +576,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         uint4 pf0[Q], pf1[Q];
         fetch(0u, pf0);
         fetch(SB, pf1);
-        const uint32_t rbias = static_cast<uint32_t>(rbase - epoch_base) - (tb + 16u);   // posbias of the region's first step
+        const uint32_t rbias = static_cast<uint32_t>(rbase - epoch_base) - (tb + 16u - 3u);   // posbias of the region's first step (the entry of a hit byte lies 3 below its address)
 
         for (uint32_t off = 0; off < rlen; off += SB) {
             if (wq_n + 64u * P + 128u + drain_early > a.wq_slab) drain();
@@ -613,16 +626,25 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
             for (int i = 0; i < K; ++i) { kx[i] = (left >> (8 * i)) & 0xffu; __builtin_assume(kx[i] < 32u); }
 
             // ---- M words of the K-grams ending at j = 0 .. P-1 (the one ending at -1 comes from the lane to the left) ----
-            uint32_t H = 0, ccnt = 0, roll = 0, mprev = 0;
+            uint32_t H = 0, ccnt = cnt32, roll = 0, mprev = 0;   // (the count sums go straight onto the region's count)
 #pragma unroll
             for (int grp = 0; grp < P / GS; ++grp) {
                 uint32_t mw[GS];
+                uint32_t qe = 0;   // K = 3: the even position's 4 c_j + 4 C c_(j-1) + offM, which the odd one behind it multiplies (gram4_index.hpp)
 #pragma unroll
                 for (int jj = 0; jj < GS; ++jj) {
                     const int j = grp * GS + jj;
-                    uint32_t x = pin4((kx[K + j] << 2) + offM);                       // 4 c_j + offM              (v_lshl_add_u32)
-                    x = mad24(kx[K + j - 1], C4, x);                                  // + 4 C c_(j-1)             (v_mad_u32_u24)
-                    if (K == 3) x = mad24(kx[K + j - 2], CC4, x);                     // + 4 C^2 c_(j-2)           (v_mad_u32_u24)
+                    uint32_t x;
+                    if (K == 3 && (jj & 1)) {
+                        x = g4i_odd(qe, kx[K + j], offM1, C);                             // C q + (4 c_j + offM - C offM): v_lshl_add_u32, v_mad_u32_u24
+                    } else if (K == 3) {
+                        const G4Idx e = g4i_even(kx[K + j], kx[K + j - 1], kx[K + j - 2], offM, C);   // v_lshl_add_u32, two v_mad_u32_u24
+                        x = e.addr;
+                        qe = e.q;
+                    } else {
+                        x = pin4((kx[K + j] << 2) + offM);                                // 4 c_j + offM              (v_lshl_add_u32)
+                        x = mad24(kx[K + j - 1], C4, x);                                  // + 4 C c_(j-1)             (v_mad_u32_u24)
+                    }
                     mw[jj] = lds_u32(x);
                 }
 #pragma unroll
@@ -632,7 +654,10 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                     // the hit bit of position j enters at the top: after the step's P - 1 shifts it sits at bit 32 - P + j
                     if (j > 0) H = __builtin_amdgcn_alignbit((jj == 0 ? mprev : mw[jj - 1]) >> kx[K + j], H, 1);   // (v_lshrrev_b32, v_alignbit_b32)
                     if ((j & 15) == 15) {  // 16 positions rolled in: sum the two-bit fields
-                        ccnt += __popc(roll & 0x55555555u) + 2u * __popc(roll & 0xaaaaaaaau);
+                        // (each field counts once, its high bit once more: v_and_b32 and two v_bcnt_u32_b32 with the sum as their addend — round 11;
+                        // low and high bits masked apart and the high count doubled took five.  Pinned: the compiler otherwise counts onto 0 and adds up)
+                        ccnt = pin4(__popc(roll) + ccnt);
+                        ccnt = pin4(__popc(roll & 0xaaaaaaaau) + ccnt);
                         roll = 0;
                     }
                 }
@@ -643,12 +668,15 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 mcarry = __builtin_amdgcn_readlane(mprev, 63);
                 H |= __builtin_amdgcn_ubfe(mleft, kx[K], 1) << (32 - P);
             }
-            cnt32 += ccnt;
+            cnt32 = ccnt;
 
             // ---- queue the hits: a wave prefix sum of the lanes' hit counts gives each lane the list index of its first one, every lane
             // then writes its own in turns (5 VALU a turn; one ballot, two mbcnt and the slot's address in every turn cost 9 before), and
             // batches of 64 are cut from the list once the step's hits are in.  A pass queues what fits; the rest waits for the next ----
-            const uint32_t text_adj = my_text - (32u - P) - tb;   // (list entries are offsets in the wave's slot: 16 bits)
+            // (list entries are LDS addresses of byte p - 3, 16 bits: my_text - 3 less the hit bit's place in H.  From the pinned lane offset, not
+            // from my_text: that form took two VGPRs more at 16 positions per lane, 65, and with them the second workgroup of a CU)
+            static_assert(P == 16 * Q, "lane_off = lane * 16 Q is this lane's offset in the step: my_text = tb + 16 + lane_off");
+            const uint32_t text_adj = tb + (lane_off - (32u - P) + 13u);
             for (;;) {
                 if (__ballot(H != 0u) == 0) break;   // (sparse text: most steps have no hit and skip the scan)
                 const uint32_t n = __popc(H);
