@@ -482,6 +482,10 @@ daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8
  *   Result: the edges on the back-pointer path from L to 0, in text order; a token is {id, start, end} with byte positions relative to
  *     the document, the document's score is best[L].  An empty document has no tokens and score +0.0f.
  * With this order and the single addition the ids, the spans and the 32 bits of every score are a function of the input alone.
+ * Against SentencePiece itself (pieces but <unk> as patterns, value = id, U+2581 written for every space by the caller, unk_score = the
+ * lowest piece score - 10, DAAC_GAP_CHARS with gap_id = unk_id) the ids are sentencepiece's with one deliberate difference: a run of
+ * unknown code points is one token per code point here, each with its span, and one unk id there; a caller that wants that list drops
+ * every unk id that follows one.  The tie order above is sentencepiece's (the longest piece into a position is met first).
  * Results follow daac_tokenize: *dev_ids holds *n_tokens u32 in device memory (NULL when there are none), dev_spans may be NULL (not
  * wanted), otherwise 2 * n_tokens u64; *n_matches = the tuples of the lattice, empty matches included; `score` (host, may be NULL)
  * receives best[L].  Buffers are released with daac_device_free.  The call returns after the stream has finished.  There is no mode: the
