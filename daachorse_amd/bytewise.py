@@ -53,6 +53,8 @@ class Split(enum.IntEnum):
     """daac_split_rule: how split_batch cuts a document into words"""
     Whitespace = 0   # \s+|\S+
     Gpt2 = 1         # GPT-2's pre-tokenizer pattern
+    Cl100k = 3       # tiktoken's cl100k_base pattern (2 is reserved)
+    Llama3 = 4       # the pattern of Llama-3's tokenizer.json
 
 
 class Match:
@@ -939,7 +941,7 @@ _default_splitters = {}
 
 
 def _default_splitter(rule):
-    rule = Split(rule) if rule in (0, 1) else rule
+    rule = Split(rule) if rule in (0, 1, 3, 4) else rule
     sp = _default_splitters.get(rule)
     if sp is None:
         sp = _default_splitters[rule] = Splitter(rule)

@@ -1,8 +1,8 @@
 // C ABI (include/daachorse_amd.h), part 12: the pre-tokenizer split of a text or a batch into words on the device (daac_splitter_create,
 // daac_split_batch, daac_split) and the gather that turns offsets over words into offsets over documents (daac_offsets_compose).  No
 // automaton is involved: a splitter is a rule and a class table.  This file validates, builds the two-stage class table on the host,
-// uploads it per device on first use, stages a host text once, marks the document starts, runs the flag pass, sums the tile counts (one
-// read-back), allocates the result and runs the write passes; the kernels are split_kernels.hip.  A single haystack is a batch of one
+// uploads it per device on first use, stages a host text once, marks the document starts, runs the flag pass (behind the two scan passes
+// where the rule has scans), sums the tile counts (one read-back), allocates the result and runs the write passes; the kernels are split_kernels.hip.  A single haystack is a batch of one
 // document.
 #include "api_internal.hpp"
 #include "batch.hpp"
@@ -39,7 +39,8 @@ daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
     return DAAC_OK;
 }
 
-const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : "whitespace"; }
+const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : "whitespace"; }
+bool rule_scans(int rule) { return rule == DAAC_SPLIT_CL100K || rule == DAAC_SPLIT_LLAMA3; }
 
 // Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
 daac_status split_precheck(const daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, bool outs_ok) {
@@ -91,10 +92,11 @@ daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t 
     a.n_docs = n;
     a.rule = sp->rule;
     a.tiles = (total + daac::kSplitTile - 1) / daac::kSplitTile;
-    // the scratch: the tile counts, their sum, the sum's scratch, the masks, the marks
+    // the scratch: the tile counts, their sum, the sum's scratch, the masks, the marks; for a rule with scans three words a tile more
     const uint64_t n_mask = a.tiles * (daac::kSplitTile / 64), n_mark = a.tiles * (daac::kSplitTile / 32) + 1, n_scan = exclusive_scan_scratch(a.tiles);
+    const uint64_t n_carry = rule_scans(sp->rule) ? 3 * a.tiles : 0;
     DevBuf work;
-    HIP_TRY(work.alloc((a.tiles + 1 + n_scan + n_mask) * sizeof(unsigned long long) + n_mark * sizeof(uint32_t), stream));
+    HIP_TRY(work.alloc((a.tiles + 1 + n_scan + n_mask) * sizeof(unsigned long long) + (n_mark + n_carry) * sizeof(uint32_t), stream));
     a.counts = static_cast<unsigned long long *>(work.p);
     unsigned long long *sum = a.counts + a.tiles, *scan_scratch = sum + 1;
     a.n_words = sum;
@@ -102,7 +104,14 @@ daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t 
     a.marks = reinterpret_cast<uint32_t *>(a.masks + n_mask);
     HIP_TRY(hipMemsetAsync(a.marks, 0, n_mark * sizeof(uint32_t), stream));
     HIP_TRY(daac::launch_split_marks(a, stream));
-    HIP_TRY(daac::launch_split_flags(a, stream));
+    if (n_carry) {
+        a.tile_sum = a.marks + n_mark;
+        a.carry_f = a.tile_sum + a.tiles;
+        a.carry_b = a.carry_f + a.tiles;
+        HIP_TRY(daac::launch_split_flags_scanned(a, stream));
+    } else {
+        HIP_TRY(daac::launch_split_flags(a, stream));
+    }
     HIP_TRY(daac::launch_exclusive_scan(a.counts, a.tiles, sum, scan_scratch, stream));
     unsigned long long words = 0;
     HIP_TRY(hipMemcpyAsync(&words, sum, sizeof(words), hipMemcpyDeviceToHost, stream));
@@ -131,7 +140,10 @@ extern "C" {
 daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out) {
     if (!out) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
     *out = nullptr;
-    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2) { set_error("rule is neither DAAC_SPLIT_WHITESPACE nor DAAC_SPLIT_GPT2"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2 && rule != DAAC_SPLIT_CL100K && rule != DAAC_SPLIT_LLAMA3) {
+        set_error("rule is none of DAAC_SPLIT_WHITESPACE, DAAC_SPLIT_GPT2, DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3");
+        return DAAC_ERR_INVALID_ARGUMENT;
+    }
     if (n_ranges && !ranges) { set_error("ranges is NULL with n_ranges = " + std::to_string(n_ranges)); return DAAC_ERR_INVALID_ARGUMENT; }
     for (size_t i = 0; i < n_ranges; ++i) {
         const daac_char_range &r = ranges[i];

@@ -6,11 +6,18 @@
 // document are the successive matches of \s+|\S+ (DAAC_SPLIT_WHITESPACE) or of GPT-2's pattern (DAAC_SPLIT_GPT2) over the units:
 // contiguous, covering the document.  Whether a word starts at a byte is decided from the bytes of its document at most kSplitBack
 // before it and kSplitAhead - 1 after it (split_kernels.hip has the local form), so the unit of parallelism is the byte.
+// DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a position that depend on runs of any length (a digit's index in its
+// run mod 3, newlines behind punctuation, a newline farther on in a whitespace run, a whitespace run that reaches the document's end):
+// segmented scans over the batch, two forwards and two backwards, in three passes that never wait for one another (split_kernels.hip).
 //
 // Positions p count from offsets[0]: 0 <= p < total = offsets[n] - offsets[0].  The scratch of a call:
 //   marks   one bit per position 0 .. total: a non-empty document starts here (bit `total`: the text ends here); set with atomicOr
 //   masks   one bit per position, kSplitTile / 64 words of 64 per tile: a word starts here
 //   counts  per tile: the set bits of its masks; their exclusive sum ranks the word starts
+// and for the two rules with scans, 12 bytes a tile:
+//   tile_sum  per tile: what the tile does to each of the four scan states, as a packed function (kSum* below)
+//   carry_f   per tile: the forward states in front of the tile's first position (kFwd*)
+//   carry_b   per tile: the backward states behind the tile's last position (kBwd*)
 #pragma once
 
 #include <cstdint>
@@ -29,6 +36,20 @@ constexpr uint32_t kSplitStage1 = 0x1100;   // entries of the class table's firs
 constexpr uint32_t kSplitBlockBytes = 64;   // a second-stage block: 256 code points, two bits each
 
 enum : uint32_t { kSplitO = 0, kSplitL = 1, kSplitN = 2, kSplitS = 3 };
+constexpr uint32_t kSplitCarryLanes = 1024;   // lanes of the one workgroup that resolves the carries across tiles
+
+// A scan state is a function of the positions in front of (forwards) or behind (backwards) a position; a position either keeps the
+// state it is handed or sets it.  What a word of 64 positions, a tile or a span of tiles does to the four states, packed:
+enum : uint32_t {
+    kSumKeepD = 1u << 0, kSumAddD = 3u << 1,   // y' = ((keep ? y : 0) + add) % 3: the units of a digit run so far, mod 3
+    kSumKeepT = 1u << 3, kSumValT = 1u << 4,   // x' = keep ? x : val: an O unit, then only newlines
+    kSumKeepF = 1u << 5, kSumValF = 1u << 6,   // f' likewise, backwards: whitespace as far as a newline
+    kSumKeepE = 1u << 7, kSumValE = 1u << 8,   // e' likewise, backwards: whitespace as far as the document's end
+    kSumFwd = kSumKeepD | kSumAddD | kSumKeepT | kSumValT,
+    kSumBwd = kSumKeepF | kSumValF | kSumKeepE | kSumValE,
+    kSumIdentity = kSumKeepD | kSumKeepT | kSumKeepF | kSumKeepE,
+};
+// the states themselves: forwards y | x << 2, backwards f | e << 1
 
 // The class of a code point from U+0080 on: (stage2[stage1[cp >> 8] * 64 + ((cp & 255) >> 2)] >> 2 * (cp & 3)) & 3.  Block 0 is all O.
 struct SplitTable {
@@ -49,6 +70,10 @@ struct SplitArgs {
     unsigned long long *counts;           // tiles: the flag pass's counts, then their exclusive sum
     const unsigned long long *n_words;    // 1: the sum of the counts
     uint64_t tiles;
+    // DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 only: tiles entries each
+    uint32_t *tile_sum;
+    uint32_t *carry_f;
+    uint32_t *carry_b;
     // the write passes
     unsigned long long *word_offsets;     // n_words + 1
     unsigned long long *doc_words;        // n_docs + 1
@@ -57,6 +82,8 @@ struct SplitArgs {
 #ifndef DAAC_SPLIT_HOST
 hipError_t launch_split_marks(const SplitArgs &a, hipStream_t stream);     // marks (zeroed by the caller)
 hipError_t launch_split_flags(const SplitArgs &a, hipStream_t stream);     // masks and counts
+// DAAC_SPLIT_CL100K / DAAC_SPLIT_LLAMA3: tile_sum, then carry_f and carry_b, then masks and counts
+hipError_t launch_split_flags_scanned(const SplitArgs &a, hipStream_t stream);
 hipError_t launch_split_scatter(const SplitArgs &a, hipStream_t stream);   // word_offsets and doc_words, the closing entries included
 // out[i] = inner[outer[i]] for i < n
 hipError_t launch_offsets_compose(const unsigned long long *inner, const unsigned long long *outer, uint64_t n, unsigned long long *out, hipStream_t stream);

@@ -26,9 +26,12 @@
 // Reads stay inside [offsets[0], offsets[n]): a staged byte outside it is 0 and no decision reads it, because position 0 and position
 // `total` carry marks.  Writes: masks and counts by the lane that owns them, word_offsets[rank] guarded by the total.
 //
+// DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 take another flag pass behind two passes of their own (sum, carry): their local form and the
+// segmented scans it reads are stated further down, in front of their functions.  The two rules above launch none of it.
+//
 // The per-position functions below are plain C++: with DAAC_SPLIT_HOST defined this file compiles without HIP and a host program
-// evaluates them at every position of documents held in buffers of exactly their size (tests/native/split_check.cpp, under ASan and
-// UBSan).
+// evaluates them at every position of documents held in buffers of exactly their size (tests/native/split_check.cpp and, for the scans,
+// tests/native/split_rules_check.cpp, under ASan and UBSan).
 #ifndef DAAC_SPLIT_HOST
 #include <hip/hip_runtime.h>
 #define SPLIT_FN static __device__ __forceinline__
@@ -137,6 +140,234 @@ SPLIT_FN void split_reach(uint32_t win, int &before, int &ahead) {
     ahead = fwd ? __builtin_ctz(fwd) + 1 : kSplitAhead;
 }
 
+// ------------------------------------------------------------------------------- DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3: the scans
+// The local form of the two rules (include/daachorse_amd.h has the patterns), over units u[i] with classes c[i]; nl(i): u[i] is 0x0A or
+// 0x0D; sp(i): u[i] is 0x20.  Four quantities depend on runs of any length, none of which crosses a document boundary:
+//   D(i), c[i] is N: the index of i in its maximal run of N units.
+//   T(i), nl(i):     the maximal run of nl units that ends at i has an O unit directly in front of it.
+//   F(i), c[i] is S: an nl unit lies behind i in the same maximal run of S units.
+//   E(i), c[i] is S: the maximal S run that holds i reaches the document's end (read by cl100k alone).
+//   sO(j): j == 0, or c[j-1] is L or N, or c[j-1] is S and not sp(j-1).
+//   K(j):  0 unless u[j] is ' and sO(j); 2 if u[j+1] folds to s t m d; 3 if u[j+1..j+2] fold to re ve ll; else 0.  Folding: an ASCII
+//          letter in either case, and U+017F for s where the table has it in class L.
+//   start(0) is true; for i > 0 the first case that applies decides:
+//     c[i] is N: start iff D(i) % 3 == 0
+//     c[i] is S: 1. nl(i) and T(i): no start           2. c[i-1] is not S, or nl(i-1) and T(i-1): start
+//                3. cl100k only, E(i): no start        4. nl(i): no start      5. F(i): no start      6. nl(i-1): start
+//                7. start iff i + 1 < n and c[i+1] is not S
+//     c[i] is L: 1. K(i-1) != 0 or K(i-2) == 3: no start                       2. K(i-2) == 2 or K(i-3) == 3: start
+//                3. c[i-1] is L: no start   4. c[i-1] is N: start   5. c[i-1] is S: start iff nl(i-1)
+//                6. c[i-1] is O: start iff not sO(i-1)
+//     c[i] is O: start iff sO(i)
+// The farthest byte read is the unit in front of a ' three bytes back (7 bytes), the farthest ahead the unit behind a whitespace unit.
+//
+// The scans run over positions, not units: every byte of a unit carries its unit's class ("filled"), so a run of units is a run of
+// positions, and a unit that straddles a tile edge needs nothing special.  Each is a state that a position either keeps or sets:
+//   y (forwards, mod 3): the unit starts of the N run up to and including p.  Set to 0 where p is not N, to 1 where a document starts
+//     at p; a unit start adds 1.  D(i) % 3 == 0 iff y == 1 at i's first byte.
+//   x (forwards): set to 1 at an O position, kept at an nl position that starts no document, else set to 0.  T(i) = nl(i) and x.
+//   f (backwards): set to 1 at an nl position, kept at another S position with no document start behind it, else set to 0.  F(i) = f
+//     at a position that is not nl.
+//   e (backwards): set to 1 at an S position with a document start (or the text's end) behind it, kept at another S position, else 0.
+// A word of 64 positions is eight masks (SplitPlanes); what it does to the four states is a packed function (kSum*, split.hpp), found
+// with count-leading and count-trailing zeros; functions compose (split_sum_then), so a tile, and a span of tiles, is a function too.
+//   sum     a workgroup per tile: the predicate bits by ballot, the words' functions, composed into tile_sum[tile].
+//   carry   one workgroup: a lane composes a span of tiles, lane 0 walks the kSplitCarryLanes spans, each lane walks its span again
+//           and writes carry_f (forwards) and carry_b (backwards).  No lane waits for another workgroup.
+//   flags   as for GPT-2, with the masks built again and the state of a position read from its word's masks and the word's carries.
+// The work at a position does not depend on the length of the run it lies in.
+
+struct SplitPlanes {
+    uint64_t un;    // a unit of class N starts here
+    uint64_t nkd;   // y is set here: not N, or a document starts here
+    uint64_t nkt;   // x is set here: not an nl that starts no document
+    uint64_t o;     // class O: what x is set to
+    uint64_t nkf;   // f is set here
+    uint64_t nl;    // nl: what f is set to
+    uint64_t nke;   // e is set here
+    uint64_t ve;    // S with a document start behind it: what e is set to
+};
+
+enum : uint32_t { kPredU = 1, kPredN = 2, kPredS = 4, kPredNl = 8, kPredO = 16 };
+
+// The predicate bits of the byte w: whether a unit starts there, the class of the unit that holds it, and nl.  before and ahead as for
+// split_start.
+SPLIT_FN uint32_t split_pred(const SplitTable &t, const uint8_t *w, int before, int ahead) {
+    const uint8_t *q = w;
+    int len = 0;
+    if ((w[0] & 0xC0u) == 0x80u)
+        for (int k = 1; k <= 3 && k <= before; ++k) {
+            const int n = split_unit_len(w - k, ahead + k);
+            if (n > k) { q = w - k; len = n; break; }
+        }
+    uint32_t bits = 0;
+    if (!len) { len = split_unit_len(w, ahead); bits = kPredU; }
+    const uint32_t c = split_class(t, q, len);
+    if (c == kSplitN) return bits | kPredN;
+    if (c == kSplitO) return bits | kPredO;
+    if (c == kSplitL) return bits;
+    return bits | kPredS | (w[0] == 0x0Au || w[0] == 0x0Du ? kPredNl : 0u);
+}
+
+// The masks of a word from the ballots of its positions: mark is "a document starts here", mark1 the same one position on.
+SPLIT_FN SplitPlanes split_planes(uint64_t u, uint64_t n, uint64_t s, uint64_t nl, uint64_t o, uint64_t mark, uint64_t mark1) {
+    SplitPlanes p;
+    p.un = u & n;
+    p.nkd = ~n | mark;
+    p.nkt = ~(nl & ~mark);
+    p.o = o;
+    p.nkf = ~(s & ~nl & ~mark1);
+    p.nl = nl;
+    p.nke = ~(s & ~mark1);
+    p.ve = s & mark1;
+    return p;
+}
+
+SPLIT_FN uint32_t split_mod3(uint32_t v) { return v % 3u; }
+SPLIT_FN uint64_t split_low(uint32_t k) { return (2ull << k) - 1ull; }   // bits 0 .. k, k < 64
+
+// What a word does to the four states.
+SPLIT_FN uint32_t split_word_sum(const SplitPlanes &p) {
+    uint32_t r = 0;
+    if (!p.nkd) r |= kSumKeepD | split_mod3(static_cast<uint32_t>(__builtin_popcountll(p.un))) << 1;
+    else r |= split_mod3(static_cast<uint32_t>(__builtin_popcountll(p.un & (~0ull << (63 - __builtin_clzll(p.nkd)))))) << 1;
+    if (!p.nkt) r |= kSumKeepT;
+    else if ((p.o >> (63 - __builtin_clzll(p.nkt))) & 1ull) r |= kSumValT;
+    if (!p.nkf) r |= kSumKeepF;
+    else if ((p.nl >> __builtin_ctzll(p.nkf)) & 1ull) r |= kSumValF;
+    if (!p.nke) r |= kSumKeepE;
+    else if ((p.ve >> __builtin_ctzll(p.nke)) & 1ull) r |= kSumValE;
+    return r;
+}
+
+// The function "first, then second" (for the backward states `first` is the part that lies behind).
+SPLIT_FN uint32_t split_sum_then(uint32_t first, uint32_t second) {
+    uint32_t r;
+    if (second & kSumKeepD) r = (first & kSumKeepD) | split_mod3(((first & kSumAddD) >> 1) + ((second & kSumAddD) >> 1)) << 1;
+    else r = second & kSumAddD;
+    r |= (second & kSumKeepT ? first : second) & (kSumKeepT | kSumValT);
+    r |= (second & kSumKeepF ? first : second) & (kSumKeepF | kSumValF);
+    r |= (second & kSumKeepE ? first : second) & (kSumKeepE | kSumValE);
+    return r;
+}
+
+// The forward states behind a part, from those in front of it, and the backward states in front of a part, from those behind it.
+SPLIT_FN uint32_t split_apply_fwd(uint32_t sum, uint32_t st) {
+    const uint32_t y = split_mod3((sum & kSumKeepD ? st & 3u : 0u) + ((sum & kSumAddD) >> 1));
+    const uint32_t x = sum & kSumKeepT ? (st >> 2) & 1u : (sum & kSumValT ? 1u : 0u);
+    return y | x << 2;
+}
+SPLIT_FN uint32_t split_apply_bwd(uint32_t sum, uint32_t st) {
+    const uint32_t f = sum & kSumKeepF ? st & 1u : (sum & kSumValF ? 1u : 0u);
+    const uint32_t e = sum & kSumKeepE ? (st >> 1) & 1u : (sum & kSumValE ? 1u : 0u);
+    return f | e << 1;
+}
+
+// What a span of parts does: the forward fields composed from its first part on, the backward fields from its last.
+SPLIT_FN uint32_t split_span_sum(const uint32_t *sum, uint64_t begin, uint64_t end) {
+    uint32_t f = kSumIdentity, b = kSumIdentity;
+    for (uint64_t i = begin; i < end; ++i) f = split_sum_then(f, sum[i]);
+    for (uint64_t i = end; i > begin; --i) b = split_sum_then(b, sum[i - 1]);
+    return (f & kSumFwd) | (b & kSumBwd);
+}
+
+// The carries of the parts of a span: carry_f[i] the forward states in front of part i given f_in in front of the span, carry_b[i] the
+// backward states behind part i given b_in behind the span.
+SPLIT_FN void split_span_carries(const uint32_t *sum, uint64_t begin, uint64_t end, uint32_t f_in, uint32_t b_in, uint32_t *carry_f, uint32_t *carry_b) {
+    for (uint64_t i = begin; i < end; ++i) { carry_f[i] = f_in; f_in = split_apply_fwd(sum[i], f_in); }
+    for (uint64_t i = end; i > begin; --i) { carry_b[i - 1] = b_in; b_in = split_apply_bwd(sum[i - 1], b_in); }
+}
+
+struct SplitScan { uint32_t y, x, x_prev, f, e; };
+
+// The states at bit k of a word: cf the forward states in front of the word, cb the backward states behind it.  x_prev is x one
+// position back.
+SPLIT_FN SplitScan split_scan_at(const SplitPlanes &p, uint32_t k, uint32_t cf, uint32_t cb) {
+    SplitScan s;
+    const uint64_t low = split_low(k), high = ~0ull << k;
+    uint64_t m = p.nkd & low;
+    if (!m) s.y = split_mod3((cf & 3u) + static_cast<uint32_t>(__builtin_popcountll(p.un & low)));
+    else s.y = split_mod3(static_cast<uint32_t>(__builtin_popcountll(p.un & low & (~0ull << (63 - __builtin_clzll(m))))));
+    m = p.nkt & low;
+    s.x = m ? static_cast<uint32_t>((p.o >> (63 - __builtin_clzll(m))) & 1ull) : (cf >> 2) & 1u;
+    m = p.nkt & (low >> 1);
+    s.x_prev = m ? static_cast<uint32_t>((p.o >> (63 - __builtin_clzll(m))) & 1ull) : (cf >> 2) & 1u;
+    m = p.nkf & high;
+    s.f = m ? static_cast<uint32_t>((p.nl >> __builtin_ctzll(m)) & 1ull) : cb & 1u;
+    m = p.nke & high;
+    s.e = m ? static_cast<uint32_t>((p.ve >> __builtin_ctzll(m)) & 1ull) : (cb >> 1) & 1u;
+    return s;
+}
+
+// The letter the unit at q folds to, as far as the contractions go (0: none of theirs); len: the unit's bytes.
+SPLIT_FN uint32_t split_fold(const SplitTable &t, const uint8_t *q, int avail, int &len) {
+    len = 1;
+    const uint32_t b = q[0];
+    if ((b | 0x20u) - 'a' < 26u) return b | 0x20u;
+    if (b == 0xC5u && avail >= 2 && q[1] == 0xBFu && split_class(t, q, 2) == kSplitL) { len = 2; return 's'; }
+    return 0;
+}
+
+// sO of the unit start q with `before` bytes of its document in front of it.
+SPLIT_FN bool split_so(const SplitTable &t, const uint8_t *q, int before) {
+    if (before <= 0) return true;
+    const int pl = split_prev_len(q, before);
+    const uint32_t pc = split_class(t, q - pl, pl);
+    if (pc == kSplitL || pc == kSplitN) return true;
+    return pc == kSplitS && q[-1] != 0x20u;
+}
+
+// K of the unit start q: `before` bytes of its document in front of it, `avail` >= 1 from q on.
+SPLIT_FN int split_contraction_fold(const SplitTable &t, const uint8_t *q, int before, int avail) {
+    if (q[0] != '\'' || avail < 2) return 0;
+    int l1;
+    const uint32_t a = split_fold(t, q + 1, avail - 1, l1);
+    int k = 0;
+    if (a == 's' || a == 't' || a == 'm' || a == 'd') k = 2;
+    else if (a && avail >= 3) {
+        const uint32_t b = q[2] | 0x20u;
+        if ((a == 'r' && b == 'e') || (a == 'v' && b == 'e') || (a == 'l' && b == 'l')) k = 3;
+    }
+    return k && split_so(t, q, before) ? k : 0;
+}
+
+// Whether a word starts at the byte w under DAAC_SPLIT_CL100K or DAAC_SPLIT_LLAMA3; before and ahead as for split_start, s the scan
+// states at w.
+SPLIT_FN bool split_start_scanned(const SplitTable &t, const uint8_t *w, int before, int ahead, int rule, const SplitScan &s) {
+    if ((w[0] & 0xC0u) == 0x80u)
+        for (int k = 1; k <= 3 && k <= before; ++k)
+            if (split_unit_len(w - k, ahead + k) > k) return false;
+    if (before == 0) return true;
+    const int len0 = split_unit_len(w, ahead);
+    const uint32_t c0 = split_class(t, w, len0);
+    if (c0 == kSplitN) return s.y == 1u;
+    const int len1 = split_prev_len(w, before);
+    const uint32_t c1 = split_class(t, w - len1, len1);
+    const bool nl1 = w[-1] == 0x0Au || w[-1] == 0x0Du;   // (a unit that ends in such a byte is that byte)
+    if (c0 == kSplitO) return c1 == kSplitL || c1 == kSplitN || (c1 == kSplitS && w[-1] != 0x20u);
+    if (c0 == kSplitS) {
+        const bool nl0 = w[0] == 0x0Au || w[0] == 0x0Du;
+        if (nl0 && s.x) return false;
+        if (c1 != kSplitS || (nl1 && s.x_prev)) return true;
+        if (rule == DAAC_SPLIT_CL100K && s.e) return false;
+        if (nl0 || s.f) return false;
+        if (nl1) return true;
+        if (len0 >= ahead) return false;
+        const int len2 = split_unit_len(w + len0, ahead - len0);
+        return split_class(t, w + len0, len2) != kSplitS;
+    }
+    // a letter: inside a contraction, behind one, or by the unit in front
+    if (split_contraction_fold(t, w - 1, before - 1, ahead + 1) != 0) return false;
+    const int k2 = before > len1 ? split_contraction_fold(t, w - len1 - 1, before - len1 - 1, ahead + len1 + 1) : 0;
+    if (k2 == 3) return false;
+    if (k2 == 2) return true;
+    if (before >= 3 && split_contraction_fold(t, w - 3, before - 3, ahead + 3) == 3) return true;
+    if (c1 == kSplitL) return false;
+    if (c1 == kSplitN) return true;
+    if (c1 == kSplitS) return nl1;
+    return !split_so(t, w - len1, before - len1);
+}
+
 #ifndef DAAC_SPLIT_HOST
 // ------------------------------------------------------------------------------------------------------- kernels and launchers
 constexpr uint32_t kSplitTileWords = kSplitTile / 64;     // mask words of a tile
@@ -229,6 +460,125 @@ __global__ __launch_bounds__(kSplitLanes) void split_scatter_kernel(const SplitA
     }
 }
 
+// ---- DAAC_SPLIT_CL100K / DAAC_SPLIT_LLAMA3: sum, carry, flags
+struct SplitTileLds {
+    uint8_t txt[kSplitTile + 32];             // entry kSplitBack + l: the byte of the tile's position l
+    uint32_t mark[kSplitMarkWords + 2];       // entry 1 + j: the tile's mark word j
+    uint64_t raw[7][kSplitTileWords];         // the ballots of the predicate bits kPredU .. kPredO, the mark and the mark one on
+    SplitPlanes pl[kSplitTileWords];
+    uint32_t wsum[kSplitTileWords];           // what each word does to the states
+    uint32_t cf[kSplitTileWords];             // the forward states in front of each word
+    uint32_t cb[kSplitTileWords];             // the backward states behind each word
+    uint32_t cnt[kSplitLanes / 64];
+};
+
+// before and ahead of the tile's position l, and the marks of the position (bit 0) and of the one behind it (bit 1)
+static __device__ __forceinline__ uint32_t split_tile_reach(const SplitTileLds &s, uint32_t l, int &before, int &ahead) {
+    const uint32_t q = l + 32u - kSplitBack;   // the bit of position p - kSplitBack in s.mark
+    const uint64_t two = static_cast<uint64_t>(s.mark[(q >> 5) + 1]) << 32 | s.mark[q >> 5];
+    const uint32_t win = static_cast<uint32_t>(two >> (q & 31u));
+    split_reach(win, before, ahead);
+    return (win >> kSplitBack) & 3u;
+}
+
+// Stages a tile and builds the masks and the functions of its words.  Ends behind a barrier.
+static __device__ __forceinline__ void split_tile_planes(const SplitArgs &a, uint64_t tile, SplitTileLds &s) {
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_mark = a.tiles * kSplitMarkWords + 1;
+    const uint64_t base = tile * kSplitTile;
+    for (uint32_t i = tid; i < kSplitTile + kSplitBack + kSplitAhead - 1; i += kSplitLanes) {
+        const uint64_t p = base + i;   // the position + kSplitBack
+        s.txt[i] = p >= static_cast<uint64_t>(kSplitBack) && p - kSplitBack < a.total ? a.text[p - kSplitBack] : static_cast<uint8_t>(0);
+    }
+    for (uint32_t i = tid; i < kSplitMarkWords + 2; i += kSplitLanes) {
+        const uint64_t w = tile * kSplitMarkWords + i;   // the word + 1
+        s.mark[i] = w >= 1 && w - 1 < n_mark ? a.marks[w - 1] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t it = 0; it < kSplitTile / kSplitLanes; ++it) {
+        const uint32_t l = it * kSplitLanes + tid;
+        uint32_t bits = 0, mk = 0;
+        if (base + l < a.total) {
+            int before, ahead;
+            mk = split_tile_reach(s, l, before, ahead);
+            bits = split_pred(a.tab, &s.txt[l + kSplitBack], before, ahead);
+        }
+        // one ballot at a time, each to LDS by the wave's first lane
+        const uint32_t all = bits | mk << 5, w = l >> 6;
+        for (uint32_t b = 0; b < 7; ++b) {
+            const uint64_t m = __ballot((all >> b) & 1u);
+            if ((tid & 63u) == 0) s.raw[b][w] = m;
+        }
+    }
+    __syncthreads();
+    if (tid < kSplitTileWords) {
+        const SplitPlanes p = split_planes(s.raw[0][tid], s.raw[1][tid], s.raw[2][tid], s.raw[3][tid], s.raw[4][tid], s.raw[5][tid], s.raw[6][tid]);
+        s.pl[tid] = p;
+        s.wsum[tid] = split_word_sum(p);
+    }
+    __syncthreads();
+}
+
+// A workgroup takes one tile (the grid's second dimension counts on behind kSplitMaxBlocks tiles): with no loop over tiles nothing of a
+// tile's work is kept in registers for the next one.
+static __device__ __forceinline__ uint64_t split_tile_of_block() { return static_cast<uint64_t>(blockIdx.y) * gridDim.x + blockIdx.x; }
+
+__global__ __launch_bounds__(kSplitLanes) void split_sum_kernel(const SplitArgs a) {
+    __shared__ SplitTileLds s;
+    const uint64_t tile = split_tile_of_block();
+    if (tile >= a.tiles) return;
+    split_tile_planes(a, tile, s);
+    if (threadIdx.x == 0) a.tile_sum[tile] = split_span_sum(s.wsum, 0, kSplitTileWords);
+}
+
+// One workgroup: lane t owns the tiles [t * chunk, (t + 1) * chunk).
+__global__ __launch_bounds__(kSplitCarryLanes) void split_carry_kernel(const SplitArgs a) {
+    __shared__ uint32_t s_sum[kSplitCarryLanes], s_f[kSplitCarryLanes], s_b[kSplitCarryLanes];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t chunk = (a.tiles + kSplitCarryLanes - 1) / kSplitCarryLanes;
+    const uint64_t begin = tid * chunk < a.tiles ? tid * chunk : a.tiles, end = begin + chunk < a.tiles ? begin + chunk : a.tiles;
+    s_sum[tid] = split_span_sum(a.tile_sum, begin, end);
+    __syncthreads();
+    if (tid == 0) split_span_carries(s_sum, 0, kSplitCarryLanes, 0u, 0u, s_f, s_b);
+    __syncthreads();
+    split_span_carries(a.tile_sum, begin, end, s_f[tid], s_b[tid], a.carry_f, a.carry_b);
+}
+
+__global__ __launch_bounds__(kSplitLanes) void split_flag_scanned_kernel(const SplitArgs a) {
+    __shared__ SplitTileLds s;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t tile = split_tile_of_block();
+    if (tile >= a.tiles) return;
+    const uint64_t base = tile * kSplitTile;
+    split_tile_planes(a, tile, s);
+    if (tid == 0) split_span_carries(s.wsum, 0, kSplitTileWords, a.carry_f[tile], a.carry_b[tile], s.cf, s.cb);
+    __syncthreads();
+    uint32_t cnt = 0;
+    for (uint32_t it = 0; it < kSplitTile / kSplitLanes; ++it) {
+        const uint32_t l = it * kSplitLanes + tid;
+        const uint64_t p = base + l;
+        bool f = false;
+        if (p < a.total) {
+            int before, ahead;
+            (void)split_tile_reach(s, l, before, ahead);
+            const SplitScan sc = split_scan_at(s.pl[l >> 6], l & 63u, s.cf[l >> 6], s.cb[l >> 6]);
+            f = split_start_scanned(a.tab, &s.txt[l + kSplitBack], before, ahead, a.rule, sc);
+        }
+        const unsigned long long m = __ballot(f);
+        if ((tid & 63u) == 0) {
+            a.masks[p >> 6] = m;
+            cnt += static_cast<uint32_t>(__popcll(m));
+        }
+    }
+    if ((tid & 63u) == 0) s.cnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long sum = 0;
+        for (uint32_t i = 0; i < kSplitLanes / 64; ++i) sum += s.cnt[i];
+        a.counts[tile] = sum;
+    }
+}
+
 // doc_words[d] = the word starts in front of document d's first position; the lane behind the last document closes both lists
 __global__ __launch_bounds__(256) void split_docs_kernel(const SplitArgs a) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
@@ -284,6 +634,18 @@ hipError_t launch_split_marks(const SplitArgs &a, hipStream_t stream) {
 
 hipError_t launch_split_flags(const SplitArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL(split_flag_kernel, dim3(split_grid(a.tiles, 1, kSplitMaxBlocks)), dim3(kSplitLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_split_flags_scanned(const SplitArgs &a, hipStream_t stream) {
+    const uint32_t gx = split_grid(a.tiles, 1, kSplitMaxBlocks), gy = static_cast<uint32_t>((a.tiles + gx - 1) / gx);   // a workgroup per tile
+    if (gy > 65535u) return hipErrorInvalidValue;   // (2^36 tiles: never)
+    hipLaunchKernelGGL(split_sum_kernel, dim3(gx, gy), dim3(kSplitLanes), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(split_carry_kernel, dim3(1), dim3(kSplitCarryLanes), 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(split_flag_scanned_kernel, dim3(gx, gy), dim3(kSplitLanes), 0, stream, a);
     return hipGetLastError();
 }
 

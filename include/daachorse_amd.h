@@ -579,14 +579,31 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  *   Classes: L (letter), N (number), S (whitespace) and O (everything else).  Below U+0080 they are fixed: A-Z a-z are L, 0-9 are N,
  *     0x09..0x0D and 0x20 are S, the rest is O.  From U+0080 on they come from the splitter's table of sorted, disjoint ranges
  *     {first, last, cls}, cls in {1 = L, 2 = N, 3 = S}; a code point in no range is O.
- *   Rules: both partition each document — its words are contiguous and cover it, nothing is dropped.
+ *   Rules: each partitions every document — its words are contiguous and cover it, nothing is dropped.
  *     DAAC_SPLIT_WHITESPACE: the words are the matches of \s+|\S+: maximal runs of S units and maximal runs of other units.
  *     DAAC_SPLIT_GPT2: the words are the successive matches of
  *       's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
  *     with \p{L} = L, \p{N} = N and \s = S, case-sensitive: the sequential scanner that tries the alternatives in order at each
  *     position, greedy, the fifth alternative backtracking.  (GPT-2, RoBERTa, BART and every byte-level BPE vocabulary trained with it.)
+ *     DAAC_SPLIT_LLAMA3: the words are the successive matches of the pattern of Llama-3's tokenizer.json,
+ *       (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ *     DAAC_SPLIT_CL100K: the words are the successive matches of tiktoken's cl100k_base pattern,
+ *       '(?i:[sdmt]|ll|ve|re)|[^\r\n\p{L}\p{N}]?+\p{L}++|\p{N}{1,3}+| ?[^\s\p{L}\p{N}]++[\r\n]*+|\s++$|\s*[\r\n]|\s+(?!\S)|\s+
+ *     In both, \p{L} = L, \p{N} = N, \s = S, \r and \n are the bytes 0x0D and 0x0A, the space is the byte 0x20, `+` behind a
+ *     quantifier makes it possessive ({1,3}+ included: up to three N units, nothing given back), and `$` is the document's end only, not
+ *     a line's.  (?i:) is Unicode simple case folding: a contraction letter matches in either ASCII case, and U+017F (LATIN SMALL LETTER
+ *     LONG S) matches s where the table has it in class L (char_classes() does); nothing else folds onto these letters (U+212A KELVIN
+ *     SIGN folds to k).  The two rules differ only at a whitespace run that reaches the document's end: cl100k's \s++$ keeps the run
+ *     as one word, Llama-3 cuts it behind its last newline.  The value 2 is reserved and refused.  (cl100k_base / GPT-4 vocabularies;
+ *     Llama-3 and the vocabularies trained with its pattern.  `tokenizers` reads {1,3}+ as a repeated interval, so for the cl100k
+ *     pattern as written it gives other words than tiktoken and this rule do: 1281 is 128|1 here.)
  *   The kernels evaluate an equivalent local form — whether a word starts at a unit follows from three units in front of it and one
  *     behind it (split_kernels.hip states it) — so the unit of parallelism is the byte.  A word start is always the first byte of a unit.
+ *     DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a unit that depend on runs of any length (a digit's index in its
+ *     run mod 3, a newline run behind punctuation, a newline farther on in a whitespace run, a whitespace run up to the document's
+ *     end): segmented scans over the batch that start again at every document, two forwards and two backwards, in two more passes —
+ *     per-tile summaries, then one workgroup that resolves the carries across tiles.  No workgroup waits for another, and the work at a
+ *     byte does not depend on the length of the run it lies in.  Scratch for them: 12 bytes per 1024 bytes of text.
  * daac_splitter_create builds a two-stage class table on the host from the ranges (n_ranges = 0: every code point from U+0080 on is O);
  * the table is uploaded per device on first use.  Status 1: a NULL out, an unknown rule, ranges that are unsorted, overlapping, have
  * last < first, first < 0x80, last > 0x10FFFF or cls outside 1..3.
@@ -597,11 +614,17 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  * Decided before a device is touched — status 1: a NULL sp, dev_word_offsets, dev_doc_words or n_words; the batch offset rules of
  * daac_scan_count_batch (host offsets; device offsets are validated as that call validates them, with one read-back).  Status 2: a
  * word list above the process-wide option max_result_bytes (8 bytes a word), answered before it is allocated.  A host haystack is
- * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=..".
+ * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=.." (rule=whitespace, gpt2, cl100k or llama3).
  * Method: one lane per document marks its first byte in a bit array; a workgroup stages a tile of 1024 bytes, 12 in front and 7 behind
  * in LDS and each lane decides its byte; a wave ballot makes a 64-bit mask word; the per-tile popcounts are summed (one read-back of
  * the total) and a second pass writes every start at its rank.  Integer work only: the result is a function of the input alone. */
-typedef enum { DAAC_SPLIT_WHITESPACE = 0, DAAC_SPLIT_GPT2 = 1 } daac_split_rule;
+typedef enum {
+    DAAC_SPLIT_WHITESPACE = 0,
+    DAAC_SPLIT_GPT2 = 1,
+    /* 2 is reserved (daac_splitter_create refuses it) */
+    DAAC_SPLIT_CL100K = 3,
+    DAAC_SPLIT_LLAMA3 = 4
+} daac_split_rule;
 typedef struct { uint32_t first, last, cls; } daac_char_range;
 typedef struct daac_splitter daac_splitter;
 daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out);

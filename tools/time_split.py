@@ -2,15 +2,17 @@
 words it makes: one JSON line.
 
 Workload: `--mib` MiB of cfg3 word soup generated on the device, as one document and cut into documents of 64 and 512 bytes.  Per shape,
-median of `--reps`, GB/s of text, all from the same run: split_batch(device=True) under both rules, a device-to-device copy of the buffer
+median of `--reps`, GB/s of text, all from the same run: split_batch(device=True) under each of `--rules`, a device-to-device copy of the buffer
 (the memory-bound yardstick the split is read against) and tokenize_bpe_batch(device=True) over (hay, word_offsets) of the GPT-2 split
 (the cfg3 dictionary, ranks = NULL), which shows what share of the pipeline the split is.  No rate is required of the call.  Where the
-word batch holds a word above bpe_doc_max the BPE column carries the refusal instead of a figure.
+word batch holds a word above bpe_doc_max the BPE column carries the refusal instead of a figure.  `--no-bpe` leaves that column out.
+Every split column also carries the fastest and the slowest of its repetitions (`*_ms_min`, `*_ms_max`): the spread a comparison between
+two builds is read against.
 
 Every GPU step — a shape's split and copy columns, then a shape's BPE column — is a child process of its own under `timeout -k 10`.
 The tool stops at the first step that fails: it writes what the steps before it gave, names the failed step and returns its status.
 
-    python tools/time_split.py [--mib 256] [--reps 3] [--out profiles/r17_split_time.json]
+    python tools/time_split.py [--mib 256] [--reps 3] [--rules whitespace,gpt2,cl100k,llama3] [--no-bpe] [--out profiles/r17_split_time.json]
 """
 import argparse
 import json
@@ -26,8 +28,7 @@ DOC_BYTES = (0, 64, 512)   # 0: the whole text as one document
 STEP_SECONDS = 300
 
 
-def timed(fn, reps):
-    import numpy as np
+def timed_all(fn, reps):
     import torch
     fn()
     torch.cuda.synchronize()
@@ -37,10 +38,15 @@ def timed(fn, reps):
         fn()
         torch.cuda.synchronize()
         ts.append(time.perf_counter() - t)
-    return float(np.median(ts))
+    return ts
 
 
-def step(doc_bytes, mib, reps, bpe_column):
+def timed(fn, reps):
+    import numpy as np
+    return float(np.median(timed_all(fn, reps)))
+
+
+def step(doc_bytes, mib, reps, bpe_column, rules):
     """one shape of the batch: the split and copy columns, or the BPE column, as one JSON line on stdout"""
     import torch
     import daachorse_amd as da
@@ -62,9 +68,9 @@ def step(doc_bytes, mib, reps, bpe_column):
     key = f"docs_of_{doc_bytes}" if doc_bytes else "one_document"
     r = {"bytes": n, "docs": off.numel() - 1, "doc_bytes": doc_bytes}
     gbs = lambda t: float(f"{n / t / 1e9:.4g}")
-    for rule in () if bpe_column else (Split.Whitespace, Split.Gpt2):
+    for name in () if bpe_column else rules:
+        rule = next(x for x in Split if x.name.lower() == name)
         sp = da.Splitter(rule)
-        name = rule.name.lower()
 
         def split():
             wo, dw = sp.split_batch(docs, device=True)
@@ -72,8 +78,10 @@ def step(doc_bytes, mib, reps, bpe_column):
             wo.free()
             dw.free()
 
-        t = timed(split, reps)
+        ts = sorted(timed_all(split, reps))
+        t = ts[len(ts) // 2] if len(ts) % 2 else (ts[len(ts) // 2 - 1] + ts[len(ts) // 2]) / 2
         r[name + "_gbs"], r[name + "_ms"] = gbs(t), round(t * 1e3, 3)
+        r[name + "_ms_min"], r[name + "_ms_max"] = round(ts[0] * 1e3, 3), round(ts[-1] * 1e3, 3)
         r["route"] = da.last_kernel()
     if not bpe_column:
         dst = torch.empty_like(hay)
@@ -117,16 +125,19 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--step", type=int, default=None, help=argparse.SUPPRESS)   # the document size, run in a child
     ap.add_argument("--bpe", action="store_true", help=argparse.SUPPRESS)       # ... that shape's BPE column
+    ap.add_argument("--rules", default="whitespace,gpt2", help="the split columns, by the lower-case names of Split")
+    ap.add_argument("--no-bpe", action="store_true", help="leave out the tokenize_bpe_batch column")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    rules = [x for x in args.rules.split(",") if x]
     if args.step is not None:
-        step(args.step, args.mib, args.reps, args.bpe)
+        step(args.step, args.mib, args.reps, args.bpe, rules)
         return
-    res = {"tool": "time_split", "mib": args.mib, "reps": args.reps}
+    res = {"tool": "time_split", "mib": args.mib, "reps": args.reps, "rules": rules}
     status = 0
-    for bpe_column in (False, True):
+    for bpe_column in (False,) if args.no_bpe else (False, True):
         for doc_bytes in DOC_BYTES:
-            cmd = [sys.executable, os.path.abspath(__file__), "--step", str(doc_bytes), "--mib", str(args.mib), "--reps", str(args.reps)] + (["--bpe"] if bpe_column else [])
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", str(doc_bytes), "--mib", str(args.mib), "--reps", str(args.reps), "--rules", args.rules] + (["--bpe"] if bpe_column else [])
             status, out = run_step(cmd, STEP_SECONDS)
             if status != 0:
                 res["failed_step"] = {"doc_bytes": doc_bytes, "bpe": bpe_column, "status": status}
