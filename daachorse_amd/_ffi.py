@@ -145,6 +145,13 @@ def lib():
     L.daac_split_batch.restype = C.c_int
     L.daac_split.argtypes = [vp, u8p, sz, C.c_int, vp, P(vp), P(C.c_uint64)]
     L.daac_split.restype = C.c_int
+    L.daac_split_words_space.argtypes = [vp, u8p, vp, sz, C.c_int, vp, P(vp)]
+    L.daac_split_words_space.restype = C.c_int
+    L.daac_tokenize_wordpiece.argtypes = [vp, C.c_int, u8p, sz, C.c_int, vp, vp, vp, sz, C.c_uint32, C.c_uint32, P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokenize_wordpiece.restype = C.c_int
+    L.daac_tokenize_wordpiece_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, P(vp), P(vp), P(vp), P(C.c_uint64),
+                                                P(C.c_uint64)]
+    L.daac_tokenize_wordpiece_batch.restype = C.c_int
     L.daac_offsets_compose.argtypes = [vp, vp, sz, vp, P(vp)]
     L.daac_offsets_compose.restype = C.c_int
     L.daac_spans_rebase.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]

@@ -55,6 +55,7 @@ class Split(enum.IntEnum):
     Gpt2 = 1         # GPT-2's pre-tokenizer pattern
     Cl100k = 3       # tiktoken's cl100k_base pattern (2 is reserved)
     Llama3 = 4       # the pattern of Llama-3's tokenizer.json
+    Bert = 6         # BERT's pre-tokenizer: whitespace runs, every punctuation character alone, runs of everything else (5 is refused)
 
 
 class Match:
@@ -767,6 +768,102 @@ class DoubleArrayAhoCorasick:
         out.append(DeviceOffsets(doc_offs.value, b.n + 1))
         return self._token_result(out, k.value, device)
 
+    # ---- tokenize_wordpiece: BERT's WordPiece (daac_tokenize_wordpiece[_batch]; Standard automata) — greedy longest-match-first over the
+    # initial pieces and the "##" continuation pieces of a word of pre-split text; a word with a position no piece covers, or of more
+    # than max_chars characters, is the one token unk_id.  `first_ids` / `cont_ids`: uint32, indexed by match value, 0xFFFFFFFF = no
+    # such piece (wordpiece_tables() makes them and the patterns from a vocabulary).
+    @staticmethod
+    def _piece_ids(name, ids):
+        a = np.ascontiguousarray(ids) if ids is not None else None
+        if a is None or a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+            raise DaachorseError(1, f"{name} must be a one-dimensional array of integers in 0 .. 0xFFFFFFFF")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def _wordpiece_model(self, first_ids, cont_ids, unk_id, max_chars):
+        f, c = self._piece_ids("first_ids", first_ids), self._piece_ids("cont_ids", cont_ids)
+        if f.size != c.size:
+            raise DaachorseError(1, f"first_ids has {f.size} entries and cont_ids {c.size}: both are indexed by match value (n_ids)")
+        if not 0 <= int(unk_id) <= 0xFFFFFFFF:
+            raise DaachorseError(1, "unk_id must be in 0 .. 0xFFFFFFFF")
+        if not 1 <= int(max_chars) <= 0xFFFFFFFF:
+            raise DaachorseError(1, "max_chars must be in 1 .. 0xFFFFFFFF")
+        keep = (f, c, np.zeros(1, dtype=np.uint32))   # (an empty table still has an address)
+        return keep, (f.ctypes.data if f.size else keep[2].ctypes.data, c.ctypes.data if c.size else keep[2].ctypes.data, f.size, int(unk_id), int(max_chars))
+
+    def tokenize_wordpiece(self, word, first_ids, cont_ids, unk_id, max_chars=100, spans=False, engine=Engine.Auto, stream=None, device=False):
+        """-> ids (np.uint32[T]), or (ids, spans) with spans=True (np.uint64[T, 2], {start, end} in bytes); device=True: the same as
+        DeviceMatches (to_numpy / free), left in device memory"""
+        h = _Haystack(word)
+        keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
+        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_wordpiece(self._h, int(engine), h.ptr, h.len, h.is_device, stream, *model, C.byref(ids),
+                                                      C.byref(sp) if spans else None, C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        return self._token_result(out, k.value, device)
+
+    def tokenize_wordpiece_batch(self, words, first_ids, cont_ids, unk_id, max_chars=100, skip=None, spans=False, engine=Engine.Auto, stream=None,
+                                 device=False):
+        """-> (ids, offsets) or (ids, spans, offsets): every document is a word, segmented on its own; word i's tokens are
+        [offsets[i], offsets[i+1]) (np.uint64[n + 1]) and its spans count from its first byte.  `skip`: None, or one byte per word
+        (a uint8 array, a uint8 CUDA tensor or the DeviceMatches of Splitter.words_space): a word whose byte is non-zero yields no
+        tokens.  device=True: DeviceMatches for ids and spans, DeviceOffsets for offsets"""
+        b = _Batch(words)
+        keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
+        skip_keep, skip_ptr = _skip_flags(skip, b.n)
+        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokenize_wordpiece_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, *model, skip_ptr, C.byref(ids),
+                                                            C.byref(sp) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
+        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+        if spans:
+            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
+        out.append(DeviceOffsets(offs.value, b.n + 1))
+        return self._token_result(out, k.value, device)
+
+    def tokenize_wordpiece_docs(self, docs, first_ids, cont_ids, unk_id, max_chars=100, split=Split.Bert, spans=False, engine=Engine.Auto, stream=None,
+                                device=False):
+        """tokenize_wordpiece behind BERT's pre-tokenizer, per document: split_batch cuts the documents into words, words_space tells
+        which of them are whitespace, tokenize_wordpiece_batch runs over (hay, word_offsets) with those words skipped and
+        daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or (ids, spans, offsets) as
+        tokenize_wordpiece_batch gives them, with document i's tokens in [offsets[i], offsets[i+1]) and spans that count from the
+        document's first byte.  `split`: a Split rule (the cached default splitter; Split.Bert's has bert_char_classes()) or a
+        Splitter.  Host documents are uploaded once.  The normalizer (clean-text, lower-casing, accent stripping) is the caller's."""
+        b = _Batch(docs)
+        if not b.is_device:
+            b = _Batch(_upload(b))
+        sp = split if isinstance(split, Splitter) else _default_splitter(split)
+        keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
+        wo, dw = sp._run(b, stream)
+        ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        n_words = wo.count - 1
+        flags = None
+        try:
+            flags = sp._words_space(b.hay, 1, wo.ptr, n_words, stream)
+            _ffi.check(_ffi.lib().daac_tokenize_wordpiece_batch(self._h, int(engine), b.hay, wo.ptr, n_words, 1, stream, *model, flags.ptr, C.byref(ids),
+                                                                C.byref(spn) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
+            out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
+            if spans:
+                out.append(DeviceMatches(spn.value, n.value, SPAN_DTYPE))
+            word_tok = DeviceOffsets(offs.value, n_words + 1)
+            try:
+                if spans and n.value:
+                    _ffi.check(_ffi.lib().daac_spans_rebase(spn.value, word_tok.ptr, wo.ptr, dw.ptr, b.off, n_words, b.n, stream))
+                _ffi.check(_ffi.lib().daac_offsets_compose(word_tok.ptr, dw.ptr, b.n + 1, stream, C.byref(doc_offs)))
+            except Exception:
+                for o in out:
+                    o.free()
+                raise
+            finally:
+                word_tok.free()
+        finally:
+            if flags is not None:
+                flags.free()
+            wo.free()
+            dw.free()
+        out.append(DeviceOffsets(doc_offs.value, b.n + 1))
+        return self._token_result(out, k.value, device)
+
     @staticmethod
     def _token_result(out, n_matches, device):
         out[0].n_matches = n_matches
@@ -851,6 +948,27 @@ def _upload(b):
     return torch.tensor(b.buf).cuda(), torch.from_numpy(b.offsets.astype(np.int64)).cuda()
 
 
+def _skip_flags(skip, n):
+    """the skip argument of tokenize_wordpiece_batch -> (what keeps it alive, its device pointer or None)"""
+    if skip is None:
+        return None, None
+    if isinstance(skip, DeviceMatches):
+        if skip.count != n or skip.dtype.itemsize != 1:
+            raise DaachorseError(1, f"skip has {skip.count} entries of {skip.dtype.itemsize} bytes for {n} words of one byte each")
+        return skip, skip.ptr
+    if hasattr(skip, "data_ptr") and hasattr(skip, "is_cuda"):
+        t = skip
+    else:
+        a = np.ascontiguousarray(skip)
+        if a.ndim != 1 or a.dtype.itemsize != 1:
+            raise DaachorseError(1, "skip must be a one-dimensional array of one byte per word (uint8)")
+        import torch
+        t = torch.from_numpy(a.view(np.uint8).copy()).cuda()
+    if not t.is_cuda or t.dtype.itemsize != 1 or not t.is_contiguous() or t.numel() != n:
+        raise DaachorseError(1, f"skip must be a contiguous uint8 CUDA tensor of one byte per word ({n})")
+    return t, (t.data_ptr() if n else None)
+
+
 _WHITE_SPACE = (0x85, 0xA0, 0x1680) + tuple(range(0x2000, 0x200B)) + (0x2028, 0x2029, 0x202F, 0x205F, 0x3000)
 _char_classes = None
 
@@ -877,6 +995,34 @@ def char_classes():
         a.setflags(write=False)
         _char_classes = a
     return _char_classes
+
+
+_bert_char_classes = None
+
+
+def bert_char_classes():
+    """The classes of the code points from U+0080 on under which Split.Bert gives the words of BERT's pre-tokenizer (`tokenizers`'
+    BertPreTokenizer): rows {first, last, cls} as char_classes() has them, with the White_Space code points in S (3), the general
+    categories P* in no range (class O: BERT punctuation, every character a word of its own), N* in N (2) and every other code point in
+    L (1) — M*, S*, C*, unassigned code points and the surrogates included, which BERT leaves inside words.  The categories are the
+    standard library's (Unicode `unicodedata.unidata_version`).  Computed once and cached (read-only)."""
+    global _bert_char_classes
+    if _bert_char_classes is None:
+        import unicodedata
+        white = frozenset(_WHITE_SPACE)
+        rows, first, cur = [], 0, 0
+        for cp in range(0x80, 0x110001):
+            c = 0
+            if cp <= 0x10FFFF:
+                c = 3 if cp in white else {"P": 0, "N": 2}.get(unicodedata.category(chr(cp))[0], 1)
+            if c != cur:
+                if cur:
+                    rows.append((first, cp - 1, cur))
+                first, cur = cp, c
+        a = np.array(rows, dtype=np.uint32).reshape(len(rows), 3)
+        a.setflags(write=False)
+        _bert_char_classes = a
+    return _bert_char_classes
 
 
 class Splitter:
@@ -915,6 +1061,37 @@ class Splitter:
         _ffi.check(_ffi.lib().daac_split(self._h, h.ptr, h.len, h.is_device, stream, C.byref(wo), C.byref(n)))
         return _offsets_result([DeviceOffsets(wo.value, n.value + 1)], device)[0]
 
+    def _words_space(self, hay_ptr, hay_is_device, wo_ptr, n_words, stream):
+        if not self._h:
+            raise DaachorseError(1, "the splitter has been freed")
+        flags = C.c_void_p()
+        _ffi.check(_ffi.lib().daac_split_words_space(self._h, hay_ptr, wo_ptr, n_words, hay_is_device, stream, C.byref(flags)))
+        return DeviceMatches(flags.value, n_words if flags.value else 0, np.dtype(np.uint8))
+
+    def words_space(self, words, stream=None, device=False):
+        """`words` = (hay, word_offsets): a haystack (host bytes or a uint8 CUDA tensor) and the n_words + 1 absolute word offsets of
+        split_batch in device memory (DeviceOffsets, or a contiguous int64 / uint64 CUDA tensor).  -> np.uint8[n_words], 1 where the
+        word is not empty and its first unit is whitespace (under Split.Whitespace and Split.Bert: the word is whitespace); device=True:
+        DeviceMatches of uint8 (to_numpy / free)"""
+        if not (isinstance(words, tuple) and len(words) == 2):
+            raise DaachorseError(1, "words_space takes (hay, word_offsets)")
+        h, wo = _Haystack(words[0]), words[1]
+        if isinstance(wo, DeviceOffsets):
+            p, cnt = wo.ptr, wo.count
+        elif hasattr(wo, "data_ptr") and wo.is_cuda and wo.dtype.itemsize == 8 and wo.is_contiguous() and wo.dim() == 1:
+            p, cnt = wo.data_ptr(), wo.numel()
+        else:
+            raise DaachorseError(1, "word_offsets are DeviceOffsets or a contiguous one-dimensional CUDA tensor of int64 / uint64")
+        if cnt < 1:
+            raise DaachorseError(1, "word_offsets hold n_words + 1 entries")
+        out = self._words_space(h.ptr, h.is_device, p, cnt - 1, stream)
+        if device:
+            return out
+        try:
+            return out.to_numpy()
+        finally:
+            out.free()
+
     def free(self):
         if self._h:
             _ffi.lib().daac_splitter_free(self._h)
@@ -941,11 +1118,37 @@ _default_splitters = {}
 
 
 def _default_splitter(rule):
-    rule = Split(rule) if rule in (0, 1, 3, 4) else rule
+    rule = Split(rule) if rule in (0, 1, 3, 4, 6) else rule
     sp = _default_splitters.get(rule)
     if sp is None:
-        sp = _default_splitters[rule] = Splitter(rule)
+        sp = _default_splitters[rule] = Splitter(rule, bert_char_classes() if rule == Split.Bert else None)
     return sp
+
+
+WORDPIECE_NONE = 0xFFFFFFFF   # in first_ids / cont_ids: no such piece
+
+
+def wordpiece_tables(vocab, prefix="##"):
+    """A WordPiece vocabulary {piece: id} (str or bytes keys) -> (patterns, first_ids, cont_ids) for tokenize_wordpiece*: `patterns` is
+    the sorted set of every key's bytes together with every key that starts with `prefix` and is longer than it, with the prefix
+    removed; first_ids[i] = vocab.get(patterns[i], 0xFFFFFFFF) and cont_ids[i] = vocab.get(prefix + patterns[i], 0xFFFFFFFF)
+    (np.uint32) — `tokenizers`' lookup: a key such as ##s is also an initial piece of the literal word "##s".  The automaton is
+    DoubleArrayAhoCorasick.new(patterns) (or the charwise one), where a pattern's value is its index."""
+    pre = _as_bytes(prefix)
+    if not pre:
+        raise DaachorseError(1, "prefix must not be empty")
+    v = {}
+    for key, i in vocab.items():
+        k = _as_bytes(key)
+        if not 0 <= int(i) < WORDPIECE_NONE:
+            raise DaachorseError(1, f"the id of {key!r} is not in 0 .. 0xFFFFFFFE")
+        if not k or k in v:
+            raise DaachorseError(1, f"the piece {key!r} is empty or comes twice")
+        v[k] = int(i)
+    patterns = sorted(set(v) | {k[len(pre):] for k in v if k.startswith(pre) and len(k) > len(pre)})
+    first = np.array([v.get(s, WORDPIECE_NONE) for s in patterns], dtype=np.uint32)
+    cont = np.array([v.get(pre + s, WORDPIECE_NONE) for s in patterns], dtype=np.uint32)
+    return patterns, first, cont
 
 
 def split_batch(docs, rule=Split.Gpt2, stream=None, device=False):

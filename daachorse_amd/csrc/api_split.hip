@@ -1,5 +1,5 @@
 // C ABI (include/daachorse_amd.h), part 12: the pre-tokenizer split of a text or a batch into words on the device (daac_splitter_create,
-// daac_split_batch, daac_split) and the gather that turns offsets over words into offsets over documents (daac_offsets_compose).  No
+// daac_split_batch, daac_split, daac_split_words_space) and the gather that turns offsets over words into offsets over documents (daac_offsets_compose).  No
 // automaton is involved: a splitter is a rule and a class table.  This file validates, builds the two-stage class table on the host,
 // uploads it per device on first use, stages a host text once, marks the document starts, runs the flag pass (behind the two scan passes
 // where the rule has scans), sums the tile counts (one read-back), allocates the result and runs the write passes; the kernels are split_kernels.hip.  A single haystack is a batch of one
@@ -39,7 +39,7 @@ daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
     return DAAC_OK;
 }
 
-const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : "whitespace"; }
+const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : rule == DAAC_SPLIT_BERT ? "bert" : "whitespace"; }
 bool rule_scans(int rule) { return rule == DAAC_SPLIT_CL100K || rule == DAAC_SPLIT_LLAMA3; }
 
 // Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
@@ -140,8 +140,8 @@ extern "C" {
 daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out) {
     if (!out) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
     *out = nullptr;
-    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2 && rule != DAAC_SPLIT_CL100K && rule != DAAC_SPLIT_LLAMA3) {
-        set_error("rule is none of DAAC_SPLIT_WHITESPACE, DAAC_SPLIT_GPT2, DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3");
+    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2 && rule != DAAC_SPLIT_CL100K && rule != DAAC_SPLIT_LLAMA3 && rule != DAAC_SPLIT_BERT) {
+        set_error("rule is none of DAAC_SPLIT_WHITESPACE, DAAC_SPLIT_GPT2, DAAC_SPLIT_CL100K, DAAC_SPLIT_LLAMA3 and DAAC_SPLIT_BERT");
         return DAAC_ERR_INVALID_ARGUMENT;
     }
     if (n_ranges && !ranges) { set_error("ranges is NULL with n_ranges = " + std::to_string(n_ranges)); return DAAC_ERR_INVALID_ARGUMENT; }
@@ -264,6 +264,38 @@ daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int ha
     const daac_status st = split_device(sp, hay, one_doc, static_cast<const unsigned long long *>(off_buf.p), 1, stream, dev_word_offsets, &doc_words, n_words);
     dev_free(doc_words, stream);
     return st;
+}
+
+daac_status daac_split_words_space(daac_splitter *sp, const uint8_t *hay, const uint64_t *dev_word_offsets, size_t n_words, int hay_is_device, void *stream_,
+                                   uint8_t **dev_flags) {
+    if (!sp || !dev_flags || (n_words && (!hay || !dev_word_offsets))) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    *dev_flags = nullptr;
+    if (n_words == 0) return DAAC_OK;
+    PmaScope scope_(nullptr);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_words > static_cast<uint64_t>(OPT(max_result_bytes))) { set_error("the flags of " + std::to_string(n_words) + " words exceed max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
+    daac::SplitTable tab{};
+    daac_status st = table_of(sp, tab);
+    if (st != DAAC_OK) return st;
+    void *staged = nullptr;
+    const uint8_t *dev_hay = hay;
+    uint64_t ends[2] = {0, ~0ull};   // what the words lie in: a device haystack is the caller's word for it
+    if (!hay_is_device) {   // the words' bytes go to the device once: the first and the last offset say which
+        HIP_TRY(hipMemcpyAsync(&ends[0], dev_word_offsets, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&ends[1], dev_word_offsets + n_words, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ends[1] < ends[0]) { set_error("word offsets decrease"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    void *flags = nullptr;
+    HIP_TRY(dev_malloc(&flags, n_words, stream));
+    std::unique_ptr<void, std::function<void(void *)>> g(flags, [stream](void *q) { dev_free(q, stream); });
+    HIP_TRY(daac::launch_split_words_space(tab, dev_hay, reinterpret_cast<const unsigned long long *>(dev_word_offsets), n_words, ends[0], ends[1],
+                                           static_cast<uint8_t *>(flags), stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *dev_flags = static_cast<uint8_t *>(g.release());
+    return DAAC_OK;
 }
 
 daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_outer, size_t n_outer, void *stream_, uint64_t **dev_out) {

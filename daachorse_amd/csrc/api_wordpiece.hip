@@ -1,0 +1,227 @@
+// C ABI (include/daachorse_amd.h), part 13: BERT's WordPiece token ids of a word or a batch of words on the device
+// (daac_tokenize_wordpiece, daac_tokenize_wordpiece_batch).  The pieces are the tuple CSR of
+// daac_scan_batch_device16(DAAC_FIND_OVERLAPPING): its engines, refusals and max_result_bytes rule are this call's; the kernels are
+// wordpiece_kernels.hip.  This file validates, stages a host text once, copies the two id tables, runs the count pass, sums the counts
+// (one read-back), allocates the result and runs the write pass.  A single haystack is a batch of one document.
+#include "api_internal.hpp"
+#include "wordpiece.hpp"
+
+namespace {
+
+// Status 1 before a device is touched.
+daac_status wp_precheck(const daac_pma *pma, const uint32_t *first_ids, const uint32_t *cont_ids, size_t n_ids, uint32_t max_chars, bool outs_ok) {
+    if (!pma || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (max_chars == 0) { set_error("max_chars is 0 (1 .. 0xFFFFFFFF; BERT has 100)"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (!first_ids) { set_error("first_ids is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (!cont_ids) { set_error("cont_ids is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    const std::vector<daac::OutputRec> &outs = pma->charwise ? pma->chost.outputs : pma->host.outputs;
+    uint64_t need = 0;   // the largest value + 1
+    for (const daac::OutputRec &o : outs) need = std::max<uint64_t>(need, static_cast<uint64_t>(o.value) + 1);
+    if (n_ids < need) { set_error("n_ids = " + std::to_string(n_ids) + " does not cover the largest match value, " + std::to_string(need - 1)); return DAAC_ERR_INVALID_ARGUMENT; }
+    return DAAC_OK;
+}
+
+daac_status doc_too_long(uint64_t d, uint64_t len) {
+    set_error("document " + std::to_string(d) + " has " + std::to_string(len) + " bytes: tokenize_wordpiece walks a document on one lane and serves fewer than 2^32 - 1 bytes");
+    return DAAC_ERR_UNSUPPORTED;
+}
+
+struct Outs {   // the caller's out-pointers; the optional ones may be NULL
+    uint32_t **dev_ids;
+    uint64_t **dev_spans;
+    uint64_t **dev_tok_offsets;   // NULL: a single haystack
+    uint64_t *n_tokens, *n_matches;
+};
+
+struct Model {
+    const uint32_t *first_ids, *cont_ids;
+    size_t n_ids;
+    uint32_t unk_id, max_chars;
+    const uint8_t *dev_skip;
+};
+
+// `dev_hay`: the haystack on the device, document 0 begins at `begin`; `len`: the bytes of all documents; `d_off`: the n + 1 offsets on
+// the device (n >= 1).  No document has 2^32 - 1 bytes or more.
+daac_status segment(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t begin, uint64_t len, const unsigned long long *d_off, uint64_t n, hipStream_t stream,
+                    const Model &m, const Outs &o) {
+    daac_match16 *list = nullptr;
+    uint64_t *doc_first = nullptr;
+    uint64_t k = 0;
+    daac_status st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream, &list, &doc_first, &k);
+    if (st != DAAC_OK) return st;
+    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
+    auto g_list = guard(list), g_first = guard(doc_first);
+
+    daac::WpArgs a{};
+    a.hay = dev_hay + begin;
+    a.seg = reinterpret_cast<const daac::WpTuple *>(list);
+    a.doc_first = reinterpret_cast<const unsigned long long *>(doc_first);
+    a.doc_off = d_off;
+    a.n_docs = n;
+    a.n_ids = m.n_ids;
+    a.unk_id = m.unk_id;
+    a.max_chars = m.max_chars;
+    a.skip = m.dev_skip;
+    // the slots (8 bytes a position), a single haystack's tok_offsets, the total, the sum's scratch, the two id tables
+    const uint64_t pos = len + n, cnt = n + 1;
+    DevBuf work;
+    HIP_TRY(work.alloc(pos * sizeof(daac::WpSlot) + (2 + cnt + exclusive_scan_scratch(cnt)) * sizeof(unsigned long long) + 2 * m.n_ids * sizeof(uint32_t), stream));
+    a.slots = static_cast<daac::WpSlot *>(work.p);
+    unsigned long long *hdr = reinterpret_cast<unsigned long long *>(a.slots + pos);
+    unsigned long long *own_off = hdr + 2;
+    unsigned long long *scan_scratch = own_off + cnt;
+    uint32_t *d_first = reinterpret_cast<uint32_t *>(scan_scratch + exclusive_scan_scratch(cnt));
+    uint32_t *d_cont = d_first + m.n_ids;
+    if (m.n_ids) {
+        HIP_TRY(hipMemcpyAsync(d_first, m.first_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_cont, m.cont_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
+    a.first_ids = d_first;
+    a.cont_ids = d_cont;
+
+    void *tok_off = nullptr;
+    if (o.dev_tok_offsets) HIP_TRY(dev_malloc(&tok_off, cnt * sizeof(uint64_t), stream));
+    auto g_off = guard(tok_off);
+    a.tok_offsets = tok_off ? static_cast<unsigned long long *>(tok_off) : own_off;
+
+    HIP_TRY(daac::launch_wordpiece_count(a, stream));
+    HIP_TRY(daac::launch_exclusive_scan(a.tok_offsets, cnt, hdr, scan_scratch, stream));
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, hdr, sizeof(total), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (total > len) { set_error("the token count does not fit the text"); return DAAC_ERR_DEVICE; }   // (never seen: every token has a byte)
+    const uint64_t per_token = sizeof(uint32_t) + (o.dev_spans ? 2 * sizeof(uint64_t) : 0);
+    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
+        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
+        return DAAC_ERR_AUTOMATON_SCALE;
+    }
+    void *ids = nullptr, *spans = nullptr;
+    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
+    auto g_ids = guard(ids);
+    if (total && o.dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
+    auto g_spans = guard(spans);
+    a.ids = static_cast<uint32_t *>(ids);
+    a.spans = static_cast<unsigned long long *>(spans);
+    if (total) HIP_TRY(daac::launch_wordpiece_write(a, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
+    g_last_kernel = "wordpiece docs=" + std::to_string(n) + " matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
+    *o.dev_ids = static_cast<uint32_t *>(g_ids.release());
+    if (o.dev_spans) *o.dev_spans = static_cast<uint64_t *>(g_spans.release());
+    if (o.dev_tok_offsets) *o.dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
+    *o.n_tokens = total;
+    *o.n_matches = k;
+    return DAAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+daac_status daac_tokenize_wordpiece(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, const uint32_t *first_ids,
+                                    const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id, uint32_t max_chars, uint32_t **dev_ids, uint64_t **dev_spans,
+                                    uint64_t *n_tokens, uint64_t *n_matches) {
+    PmaScope scope_(pma);
+    daac_status st = wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, dev_ids && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    if (len >= daac::kWpMaxDoc) return doc_too_long(0, len);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    void *staged = nullptr;
+    const uint8_t *text = hay;
+    if (!hay_is_device && len) {   // the passes read the text on the device
+        if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    DevBuf granule, off_buf;   // an empty text still gives the tuple call a buffer to point at
+    if (!len) {
+        HIP_TRY(granule.alloc(16, stream));
+        text = static_cast<const uint8_t *>(granule.p);
+    }
+    const unsigned long long one_doc[2] = {0, len};
+    HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
+    HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+    const Outs o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
+    const Model m{first_ids, cont_ids, n_ids, unk_id, max_chars, nullptr};
+    return segment(pma, engine, text, 0, len, static_cast<const unsigned long long *>(off_buf.p), 1, stream, m, o);
+}
+
+daac_status daac_tokenize_wordpiece_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
+                                          const uint32_t *first_ids, const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id, uint32_t max_chars,
+                                          const uint8_t *dev_skip, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens,
+                                          uint64_t *n_matches) {
+    PmaScope scope_(pma);
+    daac_status st = wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, dev_ids && dev_tok_offsets && n_tokens && n_matches);
+    if (st != DAAC_OK) return st;
+    // the batch calls' own argument rules
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
+    *dev_ids = nullptr;
+    if (dev_spans) *dev_spans = nullptr;
+    *dev_tok_offsets = nullptr;
+    *n_tokens = 0;
+    *n_matches = 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
+        daac_match16 *list = nullptr;
+        uint64_t *doc_first = nullptr;
+        uint64_t k = 0;
+        if ((st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, hay, offsets, 0, hay_is_device, stream_, &list, &doc_first, &k)) != DAAC_OK) return st;
+        *dev_tok_offsets = doc_first;
+        g_last_kernel = "wordpiece docs=0 matches=0 tokens=0 " + g_last_kernel;
+        return DAAC_OK;
+    }
+    if (!hay_is_device)
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] - offsets[i] >= daac::kWpMaxDoc) return doc_too_long(i, offsets[i + 1] - offsets[i]);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    // documents [offsets[0], offsets[n]) on the device, with their offsets
+    void *staged = nullptr;
+    const uint8_t *dev_hay = hay;
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
+    DevBuf off_buf;
+    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
+    if (!hay_is_device) {
+        ends[0] = offsets[0];
+        ends[1] = offsets[n];
+        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
+    if (!hay_is_device) {
+        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    } else {   // the first and last offset size the scratch; a decreasing pair in between is the tuple call's to refuse (before the count pass)
+        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ends[1] < ends[0]) { set_error("offsets decrease"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (ends[1] - ends[0] >= daac::kWpMaxDoc) {   // only then can a document of non-decreasing offsets be too long: look at them all
+            std::vector<uint64_t> h(n + 1);
+            HIP_TRY(hipMemcpyAsync(h.data(), d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            for (size_t i = 0; i < n; ++i)
+                if (h[i + 1] < h[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
+            for (size_t i = 0; i < n; ++i)
+                if (h[i + 1] - h[i] >= daac::kWpMaxDoc) return doc_too_long(i, h[i + 1] - h[i]);
+        }
+    }
+    if (!hay_is_device) d_off = static_cast<const unsigned long long *>(off_buf.p);
+    const Outs o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
+    const Model m{first_ids, cont_ids, n_ids, unk_id, max_chars, dev_skip};
+    return segment(pma, engine, dev_hay, ends[0], ends[1] - ends[0], d_off, n, stream, m, o);
+}
+
+}  // extern "C"

@@ -3,8 +3,8 @@
 // The definition (include/daachorse_amd.h has it in full).  A document is cut into units: a well-formed UTF-8 sequence (Unicode
 // Table 3-7) that lies wholly inside the document is one unit of its code point's class, every other byte a unit of class O.  The
 // classes are L, N, S and O; below U+0080 they are fixed, from U+0080 on they come from the splitter's ranges.  The words of a
-// document are the successive matches of \s+|\S+ (DAAC_SPLIT_WHITESPACE) or of GPT-2's pattern (DAAC_SPLIT_GPT2) over the units:
-// contiguous, covering the document.  Whether a word starts at a byte is decided from the bytes of its document at most kSplitBack
+// document are the successive matches of \s+|\S+ (DAAC_SPLIT_WHITESPACE) or of GPT-2's pattern (DAAC_SPLIT_GPT2) over the units, or
+// BERT's pre-tokenizer words with the whitespace runs between them (DAAC_SPLIT_BERT): contiguous, covering the document.  Whether a word starts at a byte is decided from the bytes of its document at most kSplitBack
 // before it and kSplitAhead - 1 after it (split_kernels.hip has the local form), so the unit of parallelism is the byte.
 // DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a position that depend on runs of any length (a digit's index in its
 // run mod 3, newlines behind punctuation, a newline farther on in a whitespace run, a whitespace run that reaches the document's end):
@@ -90,6 +90,10 @@ hipError_t launch_offsets_compose(const unsigned long long *inner, const unsigne
 // spans of a word batch's tokens, relative to the word, made relative to the word's document: one lane per word
 hipError_t launch_spans_rebase(unsigned long long *spans, const unsigned long long *tok_offsets, const unsigned long long *word_offsets,
                                const unsigned long long *doc_words, const unsigned long long *doc_off, uint64_t n_words, uint64_t n_docs, hipStream_t stream);
+// flags[w] = 1 iff the word [word_offsets[w], word_offsets[w+1]) of `text` (the byte that offset 0 names) is not empty and its first unit is
+// of class S; a word that is not inside [lo, hi) gets 0 and none of its bytes is read: one lane per word
+hipError_t launch_split_words_space(const SplitTable &tab, const uint8_t *text, const unsigned long long *word_offsets, uint64_t n_words, uint64_t lo, uint64_t hi,
+                                    uint8_t *flags, hipStream_t stream);
 #endif
 
 }  // namespace daac

@@ -20,6 +20,7 @@
 //     4. c[i] is L and (K(i-1) != 0 or K(i-2) == 3): no start
 //     5. K(i-2) == 2 or K(i-3) == 3: start   6. otherwise: start iff c[i] != c[i-1]
 //   DAAC_SPLIT_WHITESPACE: start(i) iff (c[i] is S) != (c[i-1] is S).
+//   DAAC_SPLIT_BERT: start(i) iff (c[i] is S) != (c[i-1] is S), or c[i] is O, or c[i-1] is O.
 // A contraction is ASCII, so K is looked up by bytes: the farthest byte read is the unit in front of a ' three bytes back (7 bytes),
 // the farthest ahead the unit behind a whitespace unit (4 + 4 bytes).
 //
@@ -30,8 +31,8 @@
 // segmented scans it reads are stated further down, in front of their functions.  The two rules above launch none of it.
 //
 // The per-position functions below are plain C++: with DAAC_SPLIT_HOST defined this file compiles without HIP and a host program
-// evaluates them at every position of documents held in buffers of exactly their size (tests/native/split_check.cpp and, for the scans,
-// tests/native/split_rules_check.cpp, under ASan and UBSan).
+// evaluates them at every position of documents held in buffers of exactly their size (tests/native/split_check.cpp, for the scans
+// tests/native/split_rules_check.cpp, for DAAC_SPLIT_BERT and split_word_space tests/native/split_bert_check.cpp, under ASan and UBSan).
 #ifndef DAAC_SPLIT_HOST
 #include <hip/hip_runtime.h>
 #define SPLIT_FN static __device__ __forceinline__
@@ -118,6 +119,7 @@ SPLIT_FN bool split_start(const SplitTable &t, const uint8_t *w, int before, int
     const uint32_t c1 = split_class(t, w - len1, len1);
     const bool s0 = c0 == kSplitS, s1 = c1 == kSplitS;
     if (rule == DAAC_SPLIT_WHITESPACE) return s0 != s1;
+    if (rule == DAAC_SPLIT_BERT) return s0 != s1 || c0 == kSplitO || c1 == kSplitO;
     if (s0 && s1) {
         if (len0 >= ahead) return false;
         const int len2 = split_unit_len(w + len0, ahead - len0);
@@ -129,6 +131,14 @@ SPLIT_FN bool split_start(const SplitTable &t, const uint8_t *w, int before, int
     if (c0 == kSplitL && (k2 == 3 || split_contraction(t, w, 1, before, ahead) != 0)) return false;
     if (k2 == 2 || split_contraction(t, w, 3, before, ahead) == 3) return true;
     return c0 != c1;
+}
+
+// Whether the word [begin, end) of `text` is whitespace: it is not empty and its first unit, taken inside the word, is of class S.
+SPLIT_FN uint8_t split_word_space(const SplitTable &t, const uint8_t *text, uint64_t begin, uint64_t end) {
+    if (end <= begin) return 0;
+    const int avail = end - begin < 4 ? static_cast<int>(end - begin) : 4;
+    const uint8_t *q = text + begin;
+    return split_class(t, q, split_unit_len(q, avail)) == kSplitS ? 1 : 0;
 }
 
 // before and ahead of a position from the mark bits around it: bit k of `win` is the mark of position p - kSplitBack + k,
@@ -622,6 +632,16 @@ __global__ __launch_bounds__(256) void spans_rebase_kernel(unsigned long long *s
     }
 }
 
+// flags[w] = whether word w is whitespace: one lane per word
+__global__ __launch_bounds__(256) void split_words_space_kernel(const SplitTable tab, const uint8_t *text, const unsigned long long *word_offsets, uint64_t n_words,
+                                                                uint64_t lo, uint64_t hi, uint8_t *flags) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t w = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; w < n_words; w += stride) {
+        const uint64_t b = word_offsets[w], e = word_offsets[w + 1];
+        flags[w] = b >= lo && e <= hi ? split_word_space(tab, text, b, e) : static_cast<uint8_t>(0);   // (a word outside the text: never, from split_batch)
+    }
+}
+
 static uint32_t split_grid(uint64_t items, uint32_t per_block, uint32_t cap) {
     const uint64_t g = (items + per_block - 1) / per_block;
     return static_cast<uint32_t>(g < 1 ? 1 : g > cap ? cap : g);
@@ -668,6 +688,13 @@ hipError_t launch_spans_rebase(unsigned long long *spans, const unsigned long lo
     if (n_words == 0 || n_docs == 0) return hipSuccess;
     hipLaunchKernelGGL(spans_rebase_kernel, dim3(split_grid(n_words, 256, 4096)), dim3(256), 0, stream, spans, tok_offsets, word_offsets, doc_words, doc_off,
                        n_words, n_docs);
+    return hipGetLastError();
+}
+
+hipError_t launch_split_words_space(const SplitTable &tab, const uint8_t *text, const unsigned long long *word_offsets, uint64_t n_words, uint64_t lo, uint64_t hi,
+                                    uint8_t *flags, hipStream_t stream) {
+    if (n_words == 0) return hipSuccess;
+    hipLaunchKernelGGL(split_words_space_kernel, dim3(split_grid(n_words, 256, 4096)), dim3(256), 0, stream, tab, text, word_offsets, n_words, lo, hi, flags);
     return hipGetLastError();
 }
 #endif

@@ -54,7 +54,9 @@ extern "C" {
  *   (6, likewise: daac_tokenize_bpe / daac_tokenize_bpe_batch — the token ids of byte-pair merging in rank order over the same tuple
  *      list, on the device — and the option bpe_doc_max.)
  *   (6, likewise: daac_splitter_create / daac_split_batch / daac_split, daac_offsets_compose and daac_spans_rebase — the pre-tokenizer
- *      split of a batch into words, on the device.) */
+ *      split of a batch into words, on the device.)
+ *   (6, likewise: daac_tokenize_wordpiece / daac_tokenize_wordpiece_batch — BERT's WordPiece over the same tuple list, on the device —
+ *      with the split rule DAAC_SPLIT_BERT and daac_split_words_space in front of it.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -594,9 +596,18 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  *     a line's.  (?i:) is Unicode simple case folding: a contraction letter matches in either ASCII case, and U+017F (LATIN SMALL LETTER
  *     LONG S) matches s where the table has it in class L (char_classes() does); nothing else folds onto these letters (U+212A KELVIN
  *     SIGN folds to k).  The two rules differ only at a whitespace run that reaches the document's end: cl100k's \s++$ keeps the run
- *     as one word, Llama-3 cuts it behind its last newline.  The value 2 is reserved and refused.  (cl100k_base / GPT-4 vocabularies;
+ *     as one word, Llama-3 cuts it behind its last newline.  The values 2 and 5 are reserved and refused.  (cl100k_base / GPT-4 vocabularies;
  *     Llama-3 and the vocabularies trained with its pattern.  `tokenizers` reads {1,3}+ as a repeated interval, so for the cl100k
  *     pattern as written it gives other words than tiktoken and this rule do: 1281 is 128|1 here.)
+ *     DAAC_SPLIT_BERT: BERT's pre-tokenizer (BasicTokenizer's whitespace and punctuation split; `tokenizers`' BertPreTokenizer) as a
+ *     partition: a maximal run of S units is a word, every O unit is a word of its own, a maximal run of L and N units is a word.  The
+ *     words that are no whitespace (daac_split_words_space tells which are) are BertPreTokenizer's words when O is BERT's punctuation.
+ *     Below U+0080 the fixed classes give that: every printable ASCII character that is neither alphanumeric nor a space is BERT
+ *     punctuation.  From U+0080 on it takes a table with the categories P* in no range and M*, S*, C* and unassigned code points in L
+ *     (the Python package's bert_char_classes()).  Two differences from `tokenizers` are deliberate.  ASCII control characters other
+ *     than 0x09..0x0D are O here and become words of their own where `tokenizers` leaves them inside words: BERT's normalizer
+ *     (clean_text) removes them before the split, which is the caller's job as lower-casing and accent stripping are.  Ill-formed UTF-8
+ *     bytes are O units, as everywhere in the splitter.  The rule looks one unit back and launches no scan.
  *   The kernels evaluate an equivalent local form — whether a word starts at a unit follows from three units in front of it and one
  *     behind it (split_kernels.hip states it) — so the unit of parallelism is the byte.  A word start is always the first byte of a unit.
  *     DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a unit that depend on runs of any length (a digit's index in its
@@ -614,7 +625,7 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  * Decided before a device is touched — status 1: a NULL sp, dev_word_offsets, dev_doc_words or n_words; the batch offset rules of
  * daac_scan_count_batch (host offsets; device offsets are validated as that call validates them, with one read-back).  Status 2: a
  * word list above the process-wide option max_result_bytes (8 bytes a word), answered before it is allocated.  A host haystack is
- * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=.." (rule=whitespace, gpt2, cl100k or llama3).
+ * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=.." (rule=whitespace, gpt2, cl100k, llama3 or bert).
  * Method: one lane per document marks its first byte in a bit array; a workgroup stages a tile of 1024 bytes, 12 in front and 7 behind
  * in LDS and each lane decides its byte; a wave ballot makes a 64-bit mask word; the per-tile popcounts are summed (one read-back of
  * the total) and a second pass writes every start at its rank.  Integer work only: the result is a function of the input alone. */
@@ -623,7 +634,9 @@ typedef enum {
     DAAC_SPLIT_GPT2 = 1,
     /* 2 is reserved (daac_splitter_create refuses it) */
     DAAC_SPLIT_CL100K = 3,
-    DAAC_SPLIT_LLAMA3 = 4
+    DAAC_SPLIT_LLAMA3 = 4,
+    /* 5 is refused, as it has been since the rules above were added */
+    DAAC_SPLIT_BERT = 6
 } daac_split_rule;
 typedef struct { uint32_t first, last, cls; } daac_char_range;
 typedef struct daac_splitter daac_splitter;
@@ -634,6 +647,14 @@ daac_status daac_split_batch(daac_splitter *sp, const uint8_t *hay, const uint64
 /* A single haystack: a batch of one document {0, len}. */
 daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
                        uint64_t **dev_word_offsets, uint64_t *n_words);
+/* Which words are whitespace: *dev_flags holds n_words bytes in device memory (daac_device_free), flags[w] = 1 iff word w =
+ * [word_offsets[w], word_offsets[w+1]) of hay is not empty and its first unit is of class S — the unit taken inside the word, by the
+ * splitter's own unit rule and class table.  Under DAAC_SPLIT_WHITESPACE and DAAC_SPLIT_BERT such a word is all S.  dev_word_offsets
+ * are n_words + 1 absolute positions in hay, in device memory, as daac_split_batch gives them; a host hay is copied to the device once
+ * (one read-back of the first and last offset).  One lane per word.  Status 1: a NULL sp or dev_flags, or a NULL hay or
+ * dev_word_offsets with n_words > 0.  n_words = 0: *dev_flags = NULL.  Returns after the stream has finished. */
+daac_status daac_split_words_space(daac_splitter *sp, const uint8_t *hay, const uint64_t *dev_word_offsets, size_t n_words, int hay_is_device,
+                                   void *stream, uint8_t **dev_flags);
 /* out[i] = inner[outer[i]] for i < n_outer, all three in device memory (*dev_out: daac_device_free).  With inner = the token offsets of
  * the word batch and outer = doc_words (n + 1 entries) it gives the token offsets per document.  Status 1: a NULL argument. */
 daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_outer, size_t n_outer, void *stream, uint64_t **dev_out);
@@ -642,6 +663,43 @@ daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_
  * the offsets that call was given.  One lane per word.  Returns after the stream has finished. */
 daac_status daac_spans_rebase(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_word_offsets, const uint64_t *dev_doc_words,
                               const uint64_t *dev_doc_offsets, size_t n_words, size_t n_docs, void *stream);
+
+/* ---- tokenize_wordpiece: BERT's WordPiece ---------------------------------------------------------------------------------------------------
+ * What `tokenizers`' models.WordPiece (and BERT's WordpieceTokenizer) computes for one word of pre-split text: greedy longest-match-first
+ * over two piece sets — the pieces a word may begin with and the "##" continuation pieces, which the text never spells out — with a
+ * word that cannot be segmented completely, or that is too long, replaced by one unknown token.  It is not daac_tokenize: that call has
+ * one piece set and emits a partial segmentation around a gap.  (BERT, DistilBERT, ELECTRA, MPNet, MiniLM and the embedding and reranker
+ * models built on them.)  Inputs: a Standard automaton (bytewise or charwise) whose patterns are the pieces without their prefix, a text
+ * or a batch whose documents are words, `first_ids` and `cont_ids` (n_ids uint32 each, indexed by match value; host arrays, copied once
+ * per call; 0xFFFFFFFF: no such piece), `unk_id`, `max_chars` (1 .. 0xFFFFFFFF; 100 in BERT) and, for the batch, `dev_skip` (NULL, or n
+ * bytes in device memory: a document whose byte is non-zero yields no tokens — the whitespace words of a split).  For a document of L
+ * bytes:
+ *   An empty or skipped document has no tokens.
+ *   If the number of bytes b with (b & 0xC0) != 0x80 exceeds max_chars, the result is the one token {unk_id, 0, L}.
+ *   Otherwise piece(s, e) is the value of the match (s, e, v) of find_overlapping_iter(doc), s < e; empty matches are not pieces.  Its id
+ *     is first_ids[v] when s == 0 and cont_ids[v] otherwise; a piece whose id is 0xFFFFFFFF does not exist in that role.
+ *   From p = 0: take the largest e such that piece(p, e) exists in its role, emit {id, p, e}, set p = e, repeat until p == L.
+ *   If some p < L has no piece, the whole document is the one token {unk_id, 0, L}.
+ * The result does not depend on the order of tuples that share an end: it is a function of the input alone.
+ * Results, out-pointers, n_matches and the batch form (dev_tok_offsets, n + 1 u64) are daac_tokenize_bpe's and daac_tokenize_bpe_batch's.
+ * Decided before a device is touched, in this order.  Status 1: a NULL pma, dev_ids, n_tokens or n_matches (the batch: dev_tok_offsets
+ * too); max_chars == 0; a NULL first_ids or cont_ids; n_ids not above the largest value among daac_pma_outputs; the batch's own offset
+ * rules, as in daac_tokenize_batch.  Status 5: a leftmost automaton.  Status 6: a document of 2^32 - 1 bytes or more (positions are kept
+ * in 32 bits, as in daac_tokenize_unigram), and the tuple call's own refusals.  Status 2: a token list above max_result_bytes (4 bytes a
+ * token, 16 more with spans), answered before it is allocated.  A host text is copied to the device once.
+ * Method: one lane per document.  Count pass: the lane clears its L + 1 slots (8 bytes per byte of text), sweeps its tuples once into
+ * best[start] = {end, id} — a tuple that exists in the role of its start replaces a shorter one — and walks p -> best[p].end; the number
+ * of hops and a one-bit verdict (segmented, or unk_id) are stored.  The counts are summed to tok_offsets and the total (one read-back),
+ * and a write pass walks best[] again.  The work of a document is L + its tuples, so there is no cap in the manner of bpe_doc_max.  No
+ * atomics, no LDS, integer work only.
+ * daac_last_kernel() says "wordpiece docs=.. matches=.. tokens=.." in front of what the tuple call reported. */
+daac_status daac_tokenize_wordpiece(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream,
+                                    const uint32_t *first_ids, const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id, uint32_t max_chars,
+                                    uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches);
+daac_status daac_tokenize_wordpiece_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device,
+                                          void *stream, const uint32_t *first_ids, const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id,
+                                          uint32_t max_chars, const uint8_t *dev_skip, uint32_t **dev_ids, uint64_t **dev_spans,
+                                          uint64_t **dev_tok_offsets, uint64_t *n_tokens, uint64_t *n_matches);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

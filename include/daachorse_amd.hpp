@@ -17,6 +17,7 @@
 // Every scan runs on the MI355X; there is no CPU scan path behind this header.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <optional>
@@ -346,6 +347,33 @@ public:
         tokenize_check(daac_tokenize_bpe_batch(h_.get(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), docs.size(), 0, nullptr,
                                                ranks.empty() ? nullptr : ranks.data(), ranks.size(), gap, gap_id, &p, nullptr, &po, &n, &k));
         std::vector<uint64_t> o(docs.size() + 1);
+        const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
+        daac_device_free(po);
+        if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
+        return {tokenize_fetch(p, n), std::move(o)};
+    }
+
+    // BERT's WordPiece (daac_tokenize_wordpiece[_batch]; Standard automata): greedy longest-match-first over the initial pieces
+    // (`first_ids[value]`) and the continuation pieces (`cont_ids[value]`; 0xFFFFFFFF: no such piece) of one word of pre-split text.  A
+    // word with a position no piece covers, or of more than `max_chars` characters, is the one token `unk_id`.  A batch segments every
+    // word on its own and returns all ids with n + 1 offsets into them.
+    std::vector<uint32_t> tokenize_wordpiece(std::string_view word, const std::vector<uint32_t> &first_ids, const std::vector<uint32_t> &cont_ids, uint32_t unk_id,
+                                             uint32_t max_chars = 100) const {
+        uint32_t *p = nullptr;
+        uint64_t n = 0, k = 0;
+        tokenize_check(daac_tokenize_wordpiece(h_.get(), DAAC_ENGINE_AUTO, reinterpret_cast<const uint8_t *>(word.data()), word.size(), 0, nullptr, first_ids.data(),
+                                               cont_ids.data(), std::min(first_ids.size(), cont_ids.size()), unk_id, max_chars, &p, nullptr, &n, &k));
+        return tokenize_fetch(p, n);
+    }
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> tokenize_wordpiece_batch(const std::vector<std::string> &words, const std::vector<uint32_t> &first_ids,
+                                                                                      const std::vector<uint32_t> &cont_ids, uint32_t unk_id,
+                                                                                      uint32_t max_chars = 100) const {
+        const Replacements d(words);
+        uint32_t *p = nullptr;
+        uint64_t *po = nullptr, n = 0, k = 0;
+        tokenize_check(daac_tokenize_wordpiece_batch(h_.get(), DAAC_ENGINE_AUTO, d.blob(), d.offs.data(), words.size(), 0, nullptr, first_ids.data(), cont_ids.data(),
+                                                     std::min(first_ids.size(), cont_ids.size()), unk_id, max_chars, nullptr, &p, nullptr, &po, &n, &k));
+        std::vector<uint64_t> o(words.size() + 1);
         const daac_status st = daac_device_to_host(o.data(), po, o.size() * sizeof(uint64_t));
         daac_device_free(po);
         if (st != DAAC_OK) { daac_device_free(p); throw PanicError(daac_last_error()); }
