@@ -152,6 +152,18 @@ def lib():
     L.daac_tokenize_wordpiece_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, P(vp), P(vp), P(vp), P(C.c_uint64),
                                                 P(C.c_uint64)]
     L.daac_tokenize_wordpiece_batch.restype = C.c_int
+    L.daac_normalizer_create.argtypes = [vp, sz, vp, sz, P(vp)]
+    L.daac_normalizer_create.restype = C.c_int
+    L.daac_normalizer_free.argtypes = [vp]
+    L.daac_normalizer_free.restype = None
+    L.daac_normalizer_table_bytes.argtypes = [vp]
+    L.daac_normalizer_table_bytes.restype = sz
+    L.daac_normalize_batch.argtypes = [vp, u8p, vp, sz, C.c_int, vp, C.c_int, P(vp), P(vp), P(vp), P(C.c_uint64)]
+    L.daac_normalize_batch.restype = C.c_int
+    L.daac_normalize.argtypes = [vp, u8p, sz, C.c_int, vp, C.c_int, P(vp), P(vp), P(C.c_uint64)]
+    L.daac_normalize.restype = C.c_int
+    L.daac_spans_to_source.argtypes = [vp, vp, vp, vp, u8p, vp, sz, sz, C.c_int, vp]
+    L.daac_spans_to_source.restype = C.c_int
     L.daac_offsets_compose.argtypes = [vp, vp, sz, vp, P(vp)]
     L.daac_offsets_compose.restype = C.c_int
     L.daac_spans_rebase.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]

@@ -822,18 +822,44 @@ class DoubleArrayAhoCorasick:
         return self._token_result(out, k.value, device)
 
     def tokenize_wordpiece_docs(self, docs, first_ids, cont_ids, unk_id, max_chars=100, split=Split.Bert, spans=False, engine=Engine.Auto, stream=None,
-                                device=False):
+                                device=False, normalizer=None):
         """tokenize_wordpiece behind BERT's pre-tokenizer, per document: split_batch cuts the documents into words, words_space tells
         which of them are whitespace, tokenize_wordpiece_batch runs over (hay, word_offsets) with those words skipped and
         daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or (ids, spans, offsets) as
         tokenize_wordpiece_batch gives them, with document i's tokens in [offsets[i], offsets[i+1]) and spans that count from the
         document's first byte.  `split`: a Split rule (the cached default splitter; Split.Bert's has bert_char_classes()) or a
-        Splitter.  Host documents are uploaded once.  The normalizer (clean-text, lower-casing, accent stripping) is the caller's."""
+        Splitter.  Host documents are uploaded once.  `normalizer`: None (the text is taken as it is) or a Normalizer, such as
+        bert_normalizer(): the documents are normalized on the device first (with src when spans=True), the chain above runs over the
+        normalized batch and spans_to_source makes the spans count from the raw document's first byte, as `tokenizers` reports
+        offsets."""
         b = _Batch(docs)
         if not b.is_device:
             b = _Batch(_upload(b))
         sp = split if isinstance(split, Splitter) else _default_splitter(split)
         keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
+        if normalizer is None:
+            out, k = self._wordpiece_docs_chain(b, sp, model, spans, engine, stream)
+            return self._token_result(out, k, device)
+        if not isinstance(normalizer, Normalizer):
+            raise DaachorseError(1, "normalizer is None or a Normalizer")
+        norm = normalizer._run(b, stream, spans)   # out, out_offsets[, src]
+        try:
+            out, k = self._wordpiece_docs_chain(_DeviceBatch(norm[0].ptr, norm[1].ptr, b.n), sp, model, spans, engine, stream)
+            if spans and out[0].count:
+                try:
+                    _ffi.check(_ffi.lib().daac_spans_to_source(out[1].ptr, out[2].ptr, norm[1].ptr, norm[2].ptr, b.hay, b.off, b.n, out[0].count, 1, stream))
+                except Exception:
+                    for o in out:
+                        o.free()
+                    raise
+        finally:
+            for o in norm:
+                o.free()
+        return self._token_result(out, k, device)
+
+    def _wordpiece_docs_chain(self, b, sp, model, spans, engine, stream):
+        """split, words_space, tokenize_wordpiece_batch, spans_rebase and offsets_compose over the device batch b -> ([ids, spans?,
+        doc_offsets] in device memory, n_matches)"""
         wo, dw = sp._run(b, stream)
         ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
         n_words = wo.count - 1
@@ -862,7 +888,7 @@ class DoubleArrayAhoCorasick:
             wo.free()
             dw.free()
         out.append(DeviceOffsets(doc_offs.value, b.n + 1))
-        return self._token_result(out, k.value, device)
+        return out, k.value
 
     @staticmethod
     def _token_result(out, n_matches, device):
@@ -927,6 +953,13 @@ class _Batch:
         self.off = self.offsets.ctypes.data
         self.n = len(parts)
         self.is_device = 0
+
+
+class _DeviceBatch:
+    """A batch the library made itself: device addresses of the text and of n + 1 offsets."""
+
+    def __init__(self, hay, off, n):
+        self.hay, self.off, self.n, self.is_device, self.keep = hay, off, n, 1, None
 
 
 def _one_granule(t):
@@ -1170,6 +1203,198 @@ def offsets_compose(inner, outer, stream=None, device=False):
     out = C.c_void_p()
     _ffi.check(_ffi.lib().daac_offsets_compose(p_in, p_out, n, stream, C.byref(out)))
     return _offsets_result([DeviceOffsets(out.value, n)], device)[0]
+
+
+class Norm(enum.IntEnum):
+    """daac_norm_kind: what a Normalizer's rule does to the code points of its range"""
+    Delete = 1     # the code point is removed
+    Replace = 2    # its image is pool[off : off + len]
+    Pad = 3        # 0x20, the character itself, 0x20
+    Hangul = 4     # the arithmetic decomposition of a Hangul syllable into jamo (inside U+AC00 .. U+D7A3 only)
+
+
+NORM_MAX_LEN = 255   # the longest image of a Replace rule, in bytes
+
+
+def _device_ptr(x, itemsize, what):
+    """(address, elements) of a DeviceMatches, DeviceOffsets or contiguous CUDA tensor with elements of `itemsize` bytes"""
+    if isinstance(x, DeviceOffsets):
+        if itemsize != 8:
+            raise DaachorseError(1, f"{what}: elements of {itemsize} bytes, not DeviceOffsets")
+        return x.ptr, x.count
+    if isinstance(x, DeviceMatches):
+        if x.dtype.itemsize % itemsize:
+            raise DaachorseError(1, f"{what}: elements of {itemsize} bytes")
+        return x.ptr, x.count * (x.dtype.itemsize // itemsize)
+    if not (hasattr(x, "data_ptr") and x.is_cuda and x.dtype.itemsize == itemsize and x.is_contiguous()):
+        raise DaachorseError(1, f"{what}: DeviceMatches, DeviceOffsets or a contiguous CUDA tensor with elements of {itemsize} bytes")
+    return x.data_ptr(), x.numel()
+
+
+class Normalizer:
+    """daac_normalizer: a per-code-point rewrite.  `rules`: rows {first, last, kind, off, len} of integers, sorted and disjoint, over
+    code points from U+0000 on, kind a Norm; `pool`: the bytes the Replace rules point into (off and len are read for them alone; len at
+    most NORM_MAX_LEN, the pool at most 2 MiB).  A code point in no rule is copied, and so is every byte that is not part of a
+    well-formed UTF-8 sequence inside its document.  bert_normalizer() makes BERT's."""
+
+    def __init__(self, rules, pool=b""):
+        self._h = None
+        a = np.asarray(rules)
+        if a.size and (a.ndim != 2 or a.shape[1] != 5 or a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise DaachorseError(1, "rules must be rows {first, last, kind, off, len} of integers in 0 .. 0xFFFFFFFF")
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 5)
+        a.setflags(write=False)
+        self.rules, self.pool = a, _as_bytes(pool)
+        pool_arr = np.frombuffer(self.pool or b"\0", dtype=np.uint8)
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().daac_normalizer_create(a.ctypes.data if a.size else None, a.shape[0], pool_arr.ctypes.data, len(self.pool), C.byref(h)))
+        self._h = h.value
+
+    @property
+    def table_bytes(self):
+        """the bytes of the two-stage table and the pool, as they are uploaded"""
+        return int(_ffi.lib().daac_normalizer_table_bytes(self._h)) if self._h else 0
+
+    def _run(self, b, stream, src):
+        """-> [out (uint8), out_offsets] or [out, out_offsets, src (uint32)], in device memory"""
+        if not self._h:
+            raise DaachorseError(1, "the normalizer has been freed")
+        out, oo, sr, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_normalize_batch(self._h, b.hay, b.off, b.n, b.is_device, stream, int(bool(src)), C.byref(out), C.byref(oo),
+                                                   C.byref(sr) if src else None, C.byref(n)))
+        res = [DeviceMatches(out.value, n.value, np.dtype(np.uint8)), DeviceOffsets(oo.value, b.n + 1)]
+        if src:
+            res.append(DeviceMatches(sr.value, n.value, np.dtype(np.uint32)))
+        return res
+
+    def normalize_batch(self, docs, src=False, stream=None, device=False):
+        """-> (out, out_offsets) or, with src=True, (out, out_offsets, src): document i's image is out[out_offsets[i] : out_offsets[i+1]]
+        (np.uint8, np.uint64[n + 1] from 0: a batch again) and src[k] (np.uint32) is the offset, from the start of its input document,
+        of the character that output byte k came from.  device=True: DeviceMatches / DeviceOffsets / DeviceMatches (to_numpy / free)"""
+        return _offsets_result(self._run(_Batch(docs), stream, src), device)
+
+    def normalize(self, haystack, src=False, stream=None, device=False):
+        """one haystack -> out, or (out, src) with src=True"""
+        h = _Haystack(haystack)
+        if not self._h:
+            raise DaachorseError(1, "the normalizer has been freed")
+        out, sr, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_normalize(self._h, h.ptr, h.len, h.is_device, stream, int(bool(src)), C.byref(out), C.byref(sr) if src else None, C.byref(n)))
+        res = [DeviceMatches(out.value, n.value, np.dtype(np.uint8))]
+        if src:
+            res.append(DeviceMatches(sr.value, n.value, np.dtype(np.uint32)))
+        res = _offsets_result(res, device)
+        return res if src else res[0]
+
+    @staticmethod
+    def spans_to_source(spans, tok_offsets, out_offsets, src, docs, stream=None):
+        """daac_spans_to_source: the {start, end} spans of tokens over the normalized batch (device memory: DeviceMatches or a CUDA
+        tensor of [T, 2] int64 / uint64; document i's are [tok_offsets[i], tok_offsets[i+1])), relative to the normalized document, are
+        rewritten in place into spans relative to the input document.  `out_offsets` and `src` are normalize_batch's (device=True),
+        `docs` the batch it was given."""
+        b = _Batch(docs)
+        p_sp, n_sp = _device_ptr(spans, 8, "spans")
+        p_to, n_to = _device_ptr(tok_offsets, 8, "tok_offsets")
+        p_oo, n_oo = _device_ptr(out_offsets, 8, "out_offsets")
+        p_sr, _ = _device_ptr(src, 4, "src")
+        if n_to != b.n + 1 or n_oo != b.n + 1 or n_sp % 2:
+            raise DaachorseError(1, f"tok_offsets and out_offsets hold n + 1 = {b.n + 1} entries and spans pairs")
+        _ffi.check(_ffi.lib().daac_spans_to_source(p_sp, p_to, p_oo, p_sr, b.hay, b.off, b.n, n_sp // 2, b.is_device, stream))
+
+    def free(self):
+        if self._h:
+            _ffi.lib().daac_normalizer_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+_CJK_BLOCKS = ((0x4E00, 0x9FFF), (0x3400, 0x4DBF), (0x20000, 0x2A6DF), (0x2A700, 0x2B73F), (0x2B740, 0x2B81F), (0x2B920, 0x2CEAF), (0xF900, 0xFAFF),
+               (0x2F800, 0x2FA1F))
+_RUST_WHITESPACE = frozenset((0x09, 0x0A, 0x0B, 0x0C, 0x0D, 0x20) + _WHITE_SPACE)   # char::is_whitespace: White_Space
+
+
+def bert_normalizer_rules(clean_text=True, handle_chinese_chars=True, strip_accents=None, lowercase=True):
+    """The rules and the pool of BERT's normalizer (`tokenizers`' BertNormalizer; BasicTokenizer's clean-up) as Normalizer takes them,
+    from the running Python's `unicodedata`: per code point the four steps composed in order —
+      clean_text: U+0000, U+FFFD and the categories Cc (but for tab, LF and CR), Cf and Co are removed (unassigned code points are
+        not); tab, LF, CR and the White_Space code points become U+0020;
+      handle_chinese_chars: a character of the CJK ideograph blocks becomes ' ' c ' ';
+      strip_accents (None: as `lowercase`): NFD, then the characters of category Mn are dropped; a Hangul syllable stays decomposed;
+      lowercase: each character's lower-case mapping, with no rule that reads context (no final sigma).
+    Adjacent code points with the same kind (and, for Replace, the same image) are one rule.  -> (np.uint32[R, 5], bytes)"""
+    import unicodedata
+    strip = bool(lowercase) if strip_accents is None else bool(strip_accents)
+    cjk = [False] * 0x110000
+    if handle_chinese_chars:
+        for lo, hi in _CJK_BLOCKS:
+            cjk[lo:hi + 1] = [True] * (hi + 1 - lo)
+    category, nfd = unicodedata.category, unicodedata.normalize
+    rows, pool, at = [], bytearray(), {}
+    run = None   # [first, last, kind, image]
+    for cp in range(0x110000):
+        kind = image = None
+        if not 0xD800 <= cp <= 0xDFFF:   # (a surrogate has no UTF-8 sequence: no rule)
+            c = s = chr(cp)
+            cat = category(c)
+            if clean_text and (cp == 0 or cp == 0xFFFD or (cat in ("Cc", "Cf", "Co") and c not in "\t\n\r")):
+                s = ""
+            else:
+                if clean_text and cp in _RUST_WHITESPACE:
+                    s = " "
+                elif cjk[cp]:
+                    s = " " + c + " "
+                if strip and s != " ":
+                    s = "".join(ch for ch in nfd("NFD", s) if category(ch) != "Mn")
+                if lowercase:
+                    s = "".join(ch.lower() for ch in s)
+            if s == c:
+                pass
+            elif s == "":
+                kind = Norm.Delete
+            elif s == " " + c + " ":
+                kind = Norm.Pad
+            elif 0xAC00 <= cp <= 0xD7A3 and s == nfd("NFD", c):
+                kind = Norm.Hangul
+            else:
+                kind, image = Norm.Replace, s.encode()
+        if run is not None and (kind, image) == (run[2], run[3]):
+            run[1] = cp
+            continue
+        if run is not None and run[2] is not None:
+            rows.append(run)
+        run = [cp, cp, kind, image]
+    if run is not None and run[2] is not None:
+        rows.append(run)
+    out = np.zeros((len(rows), 5), dtype=np.uint32)
+    for i, (first, last, kind, image) in enumerate(rows):
+        off = 0
+        if image is not None:
+            off = at.get(image)
+            if off is None:
+                off = at[image] = len(pool)
+                pool += image
+        out[i] = (first, last, int(kind), off, len(image) if image is not None else 0)
+    return out, bytes(pool)
+
+
+_bert_normalizers = {}
+
+
+def bert_normalizer(clean_text=True, handle_chinese_chars=True, strip_accents=None, lowercase=True):
+    """The Normalizer of bert_normalizer_rules(...), built once per set of options and cached.  It is `tokenizers`' BertNormalizer but
+    for three things: no canonical reordering (of the characters that survive strip_accents only 23 have a combining class, such as
+    U+302E and U+1D165: two of them side by side keep their order), bytes that are no well-formed UTF-8 are copied, and the tables are
+    those of the running Python (`unicodedata.unidata_version`)."""
+    key = (bool(clean_text), bool(handle_chinese_chars), bool(lowercase) if strip_accents is None else bool(strip_accents), bool(lowercase))
+    nz = _bert_normalizers.get(key)
+    if nz is None:
+        nz = _bert_normalizers[key] = Normalizer(*bert_normalizer_rules(*key))
+    return nz
 
 
 def scan_count_multi(pma, mode, shards, engine=Engine.Auto, checksum=True):

@@ -56,7 +56,9 @@ extern "C" {
  *   (6, likewise: daac_splitter_create / daac_split_batch / daac_split, daac_offsets_compose and daac_spans_rebase — the pre-tokenizer
  *      split of a batch into words, on the device.)
  *   (6, likewise: daac_tokenize_wordpiece / daac_tokenize_wordpiece_batch — BERT's WordPiece over the same tuple list, on the device —
- *      with the split rule DAAC_SPLIT_BERT and daac_split_words_space in front of it.) */
+ *      with the split rule DAAC_SPLIT_BERT and daac_split_words_space in front of it.)
+ *   (6, likewise: daac_normalizer_create / daac_normalize_batch / daac_normalize and daac_spans_to_source — a per-code-point rewrite of
+ *      a batch, BERT's normalizer among them, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -663,6 +665,60 @@ daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_
  * the offsets that call was given.  One lane per word.  Returns after the stream has finished. */
 daac_status daac_spans_rebase(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_word_offsets, const uint64_t *dev_doc_words,
                               const uint64_t *dev_doc_offsets, size_t n_words, size_t n_docs, void *stream);
+
+/* ---- normalize_batch: a per-code-point rewrite of a batch, on the device ------------------------------------------------------------------
+ * What a context-free normalizer computes: every character of a text replaced by a string of zero or more characters that depends on
+ * the character alone.  `tokenizers`' BertNormalizer (clean_text, handle_chinese_chars, strip_accents, lowercase) is one but for the
+ * canonical reordering of NFD (below); the Python package's bert_normalizer() builds its rules.  NFC and NFKC are not: composition
+ * reads the characters around a character.
+ * Definition.  A document is cut into the units of daac_split_batch: a well-formed UTF-8 sequence (Unicode Table 3-7) wholly inside its
+ *   document is one unit with its code point; every other byte is a unit of its own and is copied unchanged (`tokenizers` cannot be
+ *   handed such bytes: it takes a str).  Documents are independent.  The output is the concatenation, per document, of each unit's image
+ *   under the rules: a sorted, disjoint list of {first, last, kind, off, len} over code points from U+0000 on; a code point in no rule is
+ *   copied.  DAAC_NORM_DELETE: the image is empty.  DAAC_NORM_REPLACE: the image is pool[off .. off + len), the same for every code point
+ *   of the range, len <= 255, the pool at most 2^21 bytes.  DAAC_NORM_PAD: 0x20, the unit's own bytes, 0x20.  DAAC_NORM_HANGUL: the
+ *   arithmetic decomposition of a Hangul syllable into two or three jamo (Unicode 3.12), accepted only inside U+AC00 .. U+D7A3.  off and
+ *   len are read for DAAC_NORM_REPLACE alone.
+ * Deliberate differences from `tokenizers`' BertNormalizer with bert_normalizer()'s rules: no canonical reordering — after the marks of
+ *   category Mn are dropped only the 23 other characters with a non-zero combining class could be reordered (U+1B44, U+1BAA, U+1BF2,
+ *   U+1BF3, U+302E, U+302F, U+A953, U+A9C0, U+111C0, U+11235, U+1134D, U+116B6, U+1193D, U+16FF0, U+16FF1, U+1D165, U+1D166,
+ *   U+1D16D .. U+1D172), and two of them side by side stay in the order of the input; ill-formed bytes are copied; the rules follow the
+ *   Unicode version of the Python that built them.
+ * daac_normalizer_create builds a two-stage table on the host (a direct table for U+0000 .. U+007F; equal blocks of 256 code points
+ *   are stored once, so the private-use, CJK and Hangul ranges cost a block each; daac_normalizer_table_bytes says what it came to); it
+ *   is uploaded per device on first use.  Status 1: a NULL out, a NULL rules or pool with a non-zero count, rules that are unsorted or
+ *   overlap, last < first, last > 0x10FFFF, an unknown kind, a DAAC_NORM_REPLACE rule for one surrogate code point, with off + len
+ *   beyond the pool or len above 255, a pool above 2^21 bytes, DAAC_NORM_HANGUL outside its block.
+ * daac_normalize_batch: *dev_out holds *out_len bytes and *dev_out_offsets n + 1 u64 from 0, so (out, out_offsets) is a batch again;
+ *   with want_src *dev_src holds one u32 per output byte: the offset, from the start of its input document, of the unit that byte came
+ *   from (dev_src may be NULL without want_src).  All are device memory, released with daac_device_free.  The call returns after the
+ *   stream has finished.  n = 0: no byte and one offset, 0.  No byte outside [offsets[0], offsets[n]) is read.  Decided before a device is
+ *   touched — status 1: a NULL argument; the batch offset rules of daac_scan_count_batch (host offsets; device offsets are validated as
+ *   that call validates them, with one read-back).  Status 2: an output above the process-wide option max_result_bytes (one byte, with
+ *   src five bytes, per output byte), answered before it is allocated.  Status 6: with want_src, a document of 2^32 - 1 bytes or more
+ *   (host offsets: before a device is touched).  daac_last_kernel() says "normalize rules=.. docs=.. bytes=.. out=.. src=..".
+ * daac_spans_to_source rewrites n_tokens spans {start, end} that are relative to the normalized document, in place, into spans relative
+ *   to the input document, as `tokenizers` reports offsets: start -> src[start]; end -> src[end - 1] plus the length of the input unit
+ *   there (the splitter's unit rule, bounded by the document: that is why it takes the input text); an empty span at p -> src[p] twice,
+ *   with src at a document's output length read as its input length.  dev_tok_offsets (n + 1): document i's spans are
+ *   [tok_offsets[i], tok_offsets[i+1]); (hay, offsets, n, hay_is_device) is the batch daac_normalize_batch was given.  One lane per span.
+ * Method: the splitter's mark pass; a workgroup stages a tile of 1024 bytes, 3 in front and 3 behind in LDS, a lane takes four
+ *   positions, finds the units that start there and their images' lengths in the table, and the tile's sum is stored; the sums are added
+ *   up (one read-back of the total); a second pass ranks the units inside the tile and the lane that owns a unit stores its image.
+ *   Integer work only: the result is a function of the input alone. */
+typedef enum { DAAC_NORM_DELETE = 1, DAAC_NORM_REPLACE = 2, DAAC_NORM_PAD = 3, DAAC_NORM_HANGUL = 4 } daac_norm_kind;
+typedef struct { uint32_t first, last, kind, off, len; } daac_norm_rule;
+typedef struct daac_normalizer daac_normalizer;
+daac_status daac_normalizer_create(const daac_norm_rule *rules, size_t n_rules, const uint8_t *pool, size_t pool_len, daac_normalizer **out);
+void daac_normalizer_free(daac_normalizer *nz);
+size_t daac_normalizer_table_bytes(const daac_normalizer *nz);
+daac_status daac_normalize_batch(daac_normalizer *nz, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream, int want_src,
+                                 uint8_t **dev_out, uint64_t **dev_out_offsets, uint32_t **dev_src, uint64_t *out_len);
+/* A single haystack: a batch of one document {0, len}. */
+daac_status daac_normalize(daac_normalizer *nz, const uint8_t *hay, size_t len, int hay_is_device, void *stream, int want_src, uint8_t **dev_out,
+                           uint32_t **dev_src, uint64_t *out_len);
+daac_status daac_spans_to_source(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_out_offsets, const uint32_t *dev_src, const uint8_t *hay,
+                                 const uint64_t *offsets, size_t n, size_t n_tokens, int hay_is_device, void *stream);
 
 /* ---- tokenize_wordpiece: BERT's WordPiece ---------------------------------------------------------------------------------------------------
  * What `tokenizers`' models.WordPiece (and BERT's WordpieceTokenizer) computes for one word of pre-split text: greedy longest-match-first
