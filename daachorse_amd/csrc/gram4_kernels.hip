@@ -460,13 +460,18 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         const uint2 r = g.dhit_h[g4m_slot(h, g4m_f(x, mph), d, mph)];
         pend = uint4{r.x, r.y, 0u, 0u};
     };
-    // FILT, second stage: the n <= 64 survivors in lanes [0, n) of sb_* are ranked (MPH: hashed) and ask for their records
+    // FILT, second stage at the end of a scan: the n < 64 survivors still waiting in lanes [0, n) of sb_* are ranked (MPH: hashed) and ask for their
+    // records (a full set of 64 is asked for where it comes together, in process_batch)
     auto survivors_ask = [&](uint32_t n) {
         consume_pending();
         pend = uint4{0u, 0u, 0u, 0u};
         if (lane < n) { if constexpr (MPH) hash_and_ask(sb_lo); else rank_and_ask(sb_lo); }
-        fp_pos = sb_pos;
-        fp_t0 = lane < n ? sb_t0 : 0u;   // (an idle lane: nothing of it may look like a branch that goes on)
+        // (taken by moves the compiler does not see through: as plain copies fp_* and sb_* shared a name on one path and were swapped where the paths
+        // meet — round 12)
+        uint32_t t0;
+        asm("v_mov_b32_e32 %0, %1" : "=v"(fp_pos) : "v"(sb_pos));
+        asm("v_mov_b32_e32 %0, %1" : "=v"(t0) : "v"(sb_t0));
+        fp_t0 = lane < n ? t0 : 0u;   // (an idle lane: nothing of it may look like a branch that goes on)
         pend_valid = true;
     };
     auto process_batch = [&](uint32_t n) {  // n <= 64 entries: the st_n already taken out + the head of the queue
@@ -493,17 +498,30 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 const uint32_t r_pos = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_pos)));
                 const uint32_t r_lo = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_lo)));
                 const uint32_t r_t0 = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pend_t0)));
-                const bool mine = lane - sb_n < s;   // lanes [sb_n, sb_n + s) below 64: they join the waiting ones
-                sb_pos = mine ? r_pos : sb_pos;
-                sb_lo = mine ? r_lo : sb_lo;
-                sb_t0 = mine ? r_t0 : sb_t0;
-                if (sb_n + s >= 64u) {   // 64 together: ranked and asked for; what went beyond lane 63 arrived in lanes 0 .. and waits on
-                    survivors_ask(64u);
-                    sb_pos = r_pos; sb_lo = r_lo; sb_t0 = r_t0;
-                    sb_n = sb_n + s - 64u;
-                } else {
-                    sb_n += s;
+                // lanes [sb_n, sb_n + s) below 64 join the waiting ones; what went beyond lane 63 arrived in lanes [0, sb_n + s - 64).  Both as
+                // scalar masks, and every select written out on the register it keeps: sb_* stay where they are on both exits, nothing is renamed
+                // where they meet (round 12: with `mine` a per-lane compare, the select into new names and the set assigned as a whole after the
+                // 64 were asked for, the two exits met in ten and five v_mov_b32, 3.65 times a step)
+                const bool full = sb_n + s >= 64u;
+                unsigned long long mine;   // s < 64: the lanes [sb_n, sb_n + s) — one scalar instruction
+                asm("s_bfm_b64 %0, %1, %2" : "=s"(mine) : "s"(s), "s"(sb_n));
+                sb_n += s;
+                if (full) {   // 64 together: the waiting ones below the old sb_n, the arrivals from there on — hashed (ranked) and asked for straight
+                              // from the select, which leaves their position and text where the slab's store takes them from (the old ones consumed first)
+                    consume_pending();
+                    const unsigned long long upper = ~0ull << (sb_n - s);
+                    uint32_t lo64;
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(fp_pos) : "v"(sb_pos), "v"(r_pos), "s"(upper));
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lo64) : "v"(sb_lo), "v"(r_lo), "s"(upper));
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(fp_t0) : "v"(sb_t0), "v"(r_t0), "s"(upper));
+                    if constexpr (MPH) hash_and_ask(lo64); else rank_and_ask(lo64);
+                    pend_valid = true;
+                    sb_n -= 64u;
+                    asm("s_bfm_b64 %0, %1, 0" : "=s"(mine) : "s"(sb_n));   // the lanes that wrapped: [0, sb_n)
                 }
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_pos) : "v"(r_pos), "s"(mine));
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_lo) : "v"(r_lo), "s"(mine));
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_t0) : "v"(r_t0), "s"(mine));
             }
             return;
         }
