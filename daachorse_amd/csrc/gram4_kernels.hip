@@ -64,6 +64,9 @@ namespace {
 
 typedef uint32_t g4_u32x4_t __attribute__((ext_vector_type(4)));
 constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the LDS address of the byte three before the hit byte
+// batches of a pass of the FILT body at 32 / 16 positions per lane (round 13).  A pass keeps position, key bytes and text of each of its batches
+// in registers: at 16 positions per lane that would cost the 64 VGPRs and with them the second workgroup of a CU, so those instances keep one
+constexpr int kPass4Q2 = 2, kPass4Q1 = 1;
 constexpr uint32_t kProbePercent4 = 3;  // density probe: TAIL when more than 3 % of the sampled positions start a walker
 typedef __attribute__((address_space(3))) const uint32_t lds4_cu32;
 typedef __attribute__((address_space(3))) uint32_t lds4_u32;
@@ -105,6 +108,17 @@ template <typename F, int... I>
 __device__ __forceinline__ void g4_turns(F &&f, std::integer_sequence<int, I...>) {
     (void)(... && f(std::integral_constant<int, I>{}));
 }
+// f(integral_constant<int, min(n, N)>) for a wave-uniform n >= 1
+template <int N, typename F>
+__device__ __forceinline__ void g4_upto(uint32_t n, F &&f) {
+    if constexpr (N > 1) {
+        if (n < static_cast<uint32_t>(N)) {
+            g4_upto<N - 1>(n, f);
+            return;
+        }
+    }
+    f(std::integral_constant<int, N>{});
+}
 __device__ __forceinline__ unsigned long long g4_wave_sum(unsigned long long v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -144,6 +158,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     static_assert(!MPH || FILT, "the perfect hash serves the survivors of the filter");
     constexpr int P = 16 * Q;
     constexpr int GS = 8;
+    constexpr int PB = !FILT ? 1 : Q == 2 ? kPass4Q2 : kPass4Q1;   // FILT: batches of 64 hits that go through the filter in lock-step (process_pass)
     constexpr uint32_t SB = 64u * P;          // bytes a wave takes per step
     constexpr uint32_t SLOT = SB + 32u;       // [12,16) the four bytes before the step | [16, 16 + SB) the step | 16 bytes of the next
     // ONE text slot per wave: what is left in the hit queue at the end of a step (fewer than 64 entries) has its text taken out of the
@@ -538,6 +553,115 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         pend_valid = true;
     };
 
+    // FILT, round 13: the full batches a step has queued go through the filter in passes of up to PB, in lock-step: every stage of the chain —
+    // list entry, text, Bloom word, permute, each an LDS round trip that the next stage's address waits for — is asked for in ALL the pass's
+    // batches before the first answer is looked at, so a pass of NB batches waits four round trips, not 4 NB.  The body is compiled once per
+    // NB = 1 .. PB, each straight code (a stage under a per-batch branch got its wait inside the branch, in front of the next batch's read).
+    // Batch 0 takes the st_n entries already taken out plus the head of the list, the others are wholly from the list.  The ballots give every
+    // batch's pass mask, its survivor count and with them the fill of the waiting set each batch will meet (all scalar) before any permute is
+    // asked for; the joins then run in batch order exactly as process_batch's: a second set of 64 that comes together in one pass consumes
+    // the first's records before it asks for its own.  The permutes are not skipped for a batch of which nothing passes (all its lanes then
+    // target lane fill - 1; its join is skipped).  Measured forms that were slower than this one, some slower than one batch at a time
+    // (profiles/r13_gram4_decomposition.txt): the joins as one copy behind the stages of every NB, the caller's loop kept from peeling
+    // its first pass (`#pragma nounroll`), the permutes under `pm != 0`, and PB = 3 or 4.
+    auto process_pass = [&](auto nbc) {
+        constexpr int NB = decltype(nbc)::value;
+        __builtin_amdgcn_s_setprio(2);
+        // batch 0: lanes [0, st_n) hold their entry in pend_* already; they read the list's head entry like lane st_n (a queued entry: st_n < 64),
+        // so every lane's reads stay inside list and slot and no stage of the batch sits under an exec mask
+        const uint32_t i0 = static_cast<uint32_t>(std::max(static_cast<int>(lane - st_n), 0));
+        const uint32_t la = listb + ((q_head + i0) << 1);                  // batch 0's list entry; batch b >= 1: lane's own, 64 b - st_n further on
+        const uint32_t lb = listb + ((q_head + lane - st_n) << 1);
+        uint32_t t3[NB], pos[NB], lo4[NB], t0[NB];
+        // ---- all list reads ----
+        t3[0] = *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(la));
+#pragma unroll
+        for (int b = 1; b < NB; ++b) t3[b] = *reinterpret_cast<lds4_cu16 *>(static_cast<uintptr_t>(lb + 128u * b));
+        q_head += 64u * NB - st_n;
+        // ---- all text reads (the three dwords around the hit byte, as in `derive`), then the alignbytes ----
+        uint32_t d0[NB], d1[NB], d2[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const uint32_t a0 = t3[b] & ~3u;
+            d0[b] = lds_u32(a0); d1[b] = lds_u32(a0 + 4u); d2[b] = lds_u32(a0 + 8u);
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            pos[b] = t3[b] + posbias;
+            lo4[b] = __builtin_amdgcn_alignbyte(d1[b], d0[b], t3[b] & 3u);   // bytes p-3 .. p
+            t0[b] = __builtin_amdgcn_alignbyte(d2[b], d1[b], t3[b] & 3u);    // bytes p+1 .. p+4
+        }
+        {   // (st_n != 0 only in the first pass after a step that left entries behind)
+            const bool old = lane < st_n;
+            pos[0] = old ? pend_pos : pos[0];
+            lo4[0] = old ? pend_lo : lo4[0];
+            t0[0] = old ? pend_t0 : t0[0];
+            st_n = 0;
+        }
+        // ---- all probe hashes and Bloom word reads ----
+        G4Probe pr[NB];
+        uint32_t fw[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            pr[b] = g4f_probe(K == 3 ? lo4[b] : lo4[b] >> 8, t0[b] & 0xffu, bloomW);
+            fw[b] = lds_u32(offB + (pr[b].word << 2));
+        }
+        // ---- all ballots: pass masks, survivor counts and the waiting set's fill in front of every batch, on the scalar unit ----
+        unsigned long long pm[NB];
+        uint32_t fill[NB];
+        uint32_t cur = sb_n;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            pm[b] = __builtin_amdgcn_ballot_w64((pr[b].go & ~fw[b]) == 0u) | __builtin_amdgcn_ballot_w64((pr[b].ends & ~fw[b]) == 0u);
+            fill[b] = cur;
+            cur = (cur + static_cast<uint32_t>(__popcll(pm[b]))) & 63u;
+        }
+        // ---- all permute targets and permutes: survivors to lanes fill, fill + 1, .. (mod 64), the others to lane fill - 1 (process_batch) ----
+        uint32_t r_pos[NB], r_lo[NB], r_t0[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(pm[b] >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(pm[b]), 0));
+            uint32_t t;
+            asm("v_cndmask_b32_e64 %0, 63, %1, %2" : "=v"(t) : "v"(r), "s"(pm[b]));
+            const uint32_t tgt = ((t + fill[b]) << 2) & 0xfcu;
+            r_pos[b] = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(pos[b])));
+            r_lo[b] = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(lo4[b])));
+            r_t0[b] = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(static_cast<int>(tgt), static_cast<int>(t0[b])));
+        }
+        // ---- the joins, in batch order (sb_n is fill[b] when batch b's turn comes); the selects as process_batch pins them ----
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (pm[b] != 0) {
+                const uint32_t s = static_cast<uint32_t>(__popcll(pm[b]));
+                const bool full = sb_n + s >= 64u;
+                unsigned long long mine;
+                asm("s_bfm_b64 %0, %1, %2" : "=s"(mine) : "s"(s), "s"(sb_n));
+                sb_n += s;
+                if (full) {
+                    consume_pending();
+                    const unsigned long long upper = ~0ull << (sb_n - s);
+                    uint32_t lo64;
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(fp_pos) : "v"(sb_pos), "v"(r_pos[b]), "s"(upper));
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lo64) : "v"(sb_lo), "v"(r_lo[b]), "s"(upper));
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(fp_t0) : "v"(sb_t0), "v"(r_t0[b]), "s"(upper));
+                    if constexpr (MPH) hash_and_ask(lo64); else rank_and_ask(lo64);
+                    pend_valid = true;
+                    sb_n -= 64u;
+                    asm("s_bfm_b64 %0, %1, 0" : "=s"(mine) : "s"(sb_n));
+                }
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_pos) : "v"(r_pos[b]), "s"(mine));
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_lo) : "v"(r_lo[b]), "s"(mine));
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(sb_t0) : "v"(r_t0[b]), "s"(mine));
+            }
+    };
+    // the full batches queued so far: FILT with PB > 1 in passes of min(what is queued, PB), everything else one batch at a time
+    auto process_full = [&]() {
+        while (st_n + q_tail - q_head >= 64u) {
+            if constexpr (FILT && PB > 1) g4_upto<PB>((st_n + q_tail - q_head) >> 6, process_pass);
+            else process_batch(64u);
+        }
+    };
+
     uint64_t region = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave_in_wg;
     while (region < a.nregions) {
       slab_hi = static_cast<uint32_t>((region * a.region_bytes) >> 31);
@@ -716,7 +840,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 }, std::make_integer_sequence<int, P>{});
                 const uint32_t in = std::min(tot, kList4 - q_tail);
                 q_tail += in;
-                while (st_n + q_tail - q_head >= 64u) process_batch(64u);
+                process_full();
                 if (in == tot) break;
                 // more hits than the list holds: the fewer than 64 entries left move to its front and the scan runs again
                 const uint32_t n_left = q_tail - q_head;
