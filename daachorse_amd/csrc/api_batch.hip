@@ -536,9 +536,11 @@ daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // one offset, 0
         void *z = nullptr;
-        HIP_TRY(hipMalloc(&z, sizeof(uint64_t)));
-        HIP_TRY(hipMemset(z, 0, sizeof(uint64_t)));
-        *dev_doc_offsets = static_cast<uint64_t *>(z);
+        HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
+        std::unique_ptr<void, std::function<void(void *)>> g_z(z, [stream](void *q) { dev_free(q, stream); });
+        HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        *dev_doc_offsets = static_cast<uint64_t *>(g_z.release());
         report(bp, Route{});
         return DAAC_OK;
     }
@@ -589,9 +591,11 @@ daac_status daac_scan_histogram_batch(daac_pma *pma, int mode, int engine, const
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // one offset, 0
         void *z = nullptr;
-        HIP_TRY(hipMalloc(&z, sizeof(uint64_t)));
-        HIP_TRY(hipMemset(z, 0, sizeof(uint64_t)));
-        *dev_doc_offsets = static_cast<uint64_t *>(z);
+        HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
+        std::unique_ptr<void, std::function<void(void *)>> g_z(z, [stream](void *q) { dev_free(q, stream); });
+        HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        *dev_doc_offsets = static_cast<uint64_t *>(g_z.release());
         report_hist(bp, HistRoute{});
         return DAAC_OK;
     }
