@@ -50,6 +50,8 @@ const char *last_error_cstr();
     X(gram_lds_budget, 158 * 1024, 1)                                                                                                        \
     X(gram_region, 0, 0)                 /* 0 = auto: 16 KiB for the first table set, 64 / 256 KiB for the second */                         \
     X(gram_slab, 4096, 0)                                                                                                                    \
+    X(gram_region_small, 0, 0)           /* gram4: bytes of the small regions at the haystack's end (0 = auto: 32 KiB; a power of two <= gram_region) */ \
+    X(gram_taper_split, -1, 0)           /* gram4: the byte the small regions begin at, rounded down to a region (-1 = auto; past the end: none) */ \
     X(gram_ppl, 0, 0)                    /* 0 = auto, 16, 32 positions per lane and step */                                                  \
     X(gram_dense, -1, 0)                 /* -1 = decide per automaton */                                                                     \
     X(gram_rank_in_lds, -1, 1)           /* -1 = decide per automaton */                                                                     \

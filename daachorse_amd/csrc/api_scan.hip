@@ -1,6 +1,11 @@
 // C ABI (include/daachorse_amd.h), part 2: the scan drivers — plans, the chain walkers' passes, ranged scans that leave their tuple list on the
 // device or hand it to the host, count (+ checksum) incl. shards and several devices.  No CPU scan fallback lives here.
 #include "api_internal.hpp"
+#include "gram4_claims.hpp"
+
+// gram4's small regions at the haystack's end, by default (the sizes and shares tried)
+static constexpr int64_t kTaperSmall = 32768;     // bytes of a small region
+static constexpr uint64_t kTaperPerWave = 2;      // small regions per wave of a full launch
 
 static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, size_t begin, int hay_is_device,
                                    void *stream_, uint64_t *count, uint64_t *checksum, uint64_t *result_dev, bool want_checksum);
@@ -452,12 +457,12 @@ std::pair<int, int> count_ids(const DeviceTables *t, const CountPlan &cp) {
 }
 
 // what daac_last_kernel() says: the kernel family and, for the `.count()` kernel, the launch shape the options gave it
-static std::string count_kernel_name(const CountPlan &cp) {
+static std::string count_kernel_name(const CountPlan &cp, const std::string &regions = std::string()) {
     static const char *const family[] = {"gram4", "gram", "gram2", "gram2w", "pfx"};
     if (cp.kernel == CountKernel::walkers) return cp.charwise ? "charwise" : cp.tier ? "tiered" : "darray";
     if (cp.kernel != CountKernel::gram4) return family[static_cast<int>(cp.kernel)];
     return "gram4 ppl=" + std::to_string(cp.ppl) + " dir=" + std::to_string(cp.g4.dir) + " waves=" + std::to_string(cp.g4.threads / 64) + " arith=" +
-           std::to_string(cp.g4.arith) + " filter=" + std::to_string(cp.g4.filter) + " mph=" + std::to_string(cp.g4.mph) + " tail=" + (OPT(gram_tail) < 0 ? std::string("auto") : std::to_string(OPT(gram_tail) > 0 ? 1 : 0));
+           std::to_string(cp.g4.arith) + " filter=" + std::to_string(cp.g4.filter) + " mph=" + std::to_string(cp.g4.mph) + regions + " tail=" + (OPT(gram_tail) < 0 ? std::string("auto") : std::to_string(OPT(gram_tail) > 0 ? 1 : 0));
 }
 
 }  // namespace api
@@ -521,7 +526,9 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
     dbg_mark("count: find3 back");
     ChainBuffers chain_buffers;
     if (!find3_served && pl.a.nseg != 0 && (st = chain_resolve(pma, t, pl, stream, chain_buffers)) != DAAC_OK) return st;
-    if (!find3_served) HIP_TRY(hipMemsetAsync(d_res, 0, 3 * sizeof(unsigned long long), stream));
+    // (the gram4 kernel stores its result — its last workgroup does, from the call's own counters — and needs no clear of d_res in front of it)
+    const bool g4_launch = cp.kernel == CountKernel::gram4 && len != begin;
+    if (!find3_served && !g4_launch) HIP_TRY(hipMemsetAsync(d_res, 0, 3 * sizeof(unsigned long long), stream));
     void *flagbuf = nullptr;
     if (pl.leftmost && pma->root_has_output()) {  // the one scan that can hit the non-terminating corner
         HIP_TRY(hipMalloc(&flagbuf, sizeof(unsigned long long)));
@@ -552,23 +559,67 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
         assert((region & (region - 1)) == 0 && region <= (1ull << 30));
         ga.ppl = cp.ppl;
         ga.region_bytes = region;
-        ga.nregions = (ga.vlen + region - 1) / region;
         ga.result = d_res;
         const uint32_t threads = cp.threads, wpb = threads / 64;
         uint32_t bpc = static_cast<uint32_t>(OPT(blocks_per_cu));
         if (bpc == 0) bpc = std::max(1u, std::min(2048u / threads, (160u * 1024u) / cp.lds_bytes));
+        // gram4 claims its regions from a counter (gram4_claims.hpp) and the haystack's end is cut into small regions, so that the waves finish
+        // together: by default kTaperPerWave regions of 32 KiB per wave of a full launch (256 MiB of a 4 GiB scan; a small region pays the
+        // region start for fewer bytes, which is why only the end is cut this way).  Options gram_region_small / gram_taper_split decide otherwise.
+        uint64_t small = region, split = ~0ull;
+        if (g4_launch) {
+            const uint64_t full_waves = static_cast<uint64_t>(t->num_cu) * bpc * wpb;
+            small = 2048;
+            const int64_t small_opt = OPT(gram_region_small) > 0 ? OPT(gram_region_small) : kTaperSmall;
+            while (small * 2 <= static_cast<uint64_t>(small_opt) && small * 2 <= region) small *= 2;
+            if (OPT(gram_taper_split) >= 0) {
+                split = static_cast<uint64_t>(OPT(gram_taper_split));
+            } else if (small < region) {
+                // (only where two whole rounds of large regions stay in front of the tail: with fewer, the waves reach the counter together —
+                // 2 GiB, two regions per wave, ran 9 % slower with a tail than without)
+                const uint64_t tail = full_waves * kTaperPerWave * small;
+                if (ga.vlen > tail && (ga.vlen - tail) / region >= 2 * full_waves) split = ga.vlen - tail;
+            }
+        }
+        const G4Taper taper = g4_taper_plan(ga.vlen, region, small, split);
+        ga.region_small = taper.small;
+        ga.nlarge = taper.nlarge;
+        ga.nregions = taper.nregions;   // (the other kernels: all of them large)
         const uint32_t blocks = static_cast<uint32_t>(
             std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(t->num_cu) * bpc, (ga.nregions + wpb - 1) / wpb)));
         // room for what one step can queue at worst (64 * ppl + 128 walkers) on top of a useful fill level
         ga.wq_slab = static_cast<uint32_t>(std::max<int64_t>(64 * ga.ppl + 128 + 64, OPT(gram_slab)));  // (a step can queue 64 * ppl walkers)
+        // gram4: every whole round of large regions is static (wave + k * nwaves), what is left of them and the small regions are claimed —
+        // the waves start together, and claims made together queue at the counter (4 096 adds to one address: 60 us).  Without small
+        // regions nothing is claimed: every region is static, as until round 14 (a claim per wave at the start cost cfg2's 0.1 ms scan 40 %).
+        ga.static_rounds = ga.nlarge == ga.nregions ? ~0u : static_cast<uint32_t>(std::max<uint64_t>(1, ga.nlarge / (static_cast<uint64_t>(blocks) * wpb)));
+        if (g4_launch) {
+            // the kernel keeps region indices and claims in 32 bits: every wave claims once more than it scans
+            if (ga.nregions + static_cast<uint64_t>(blocks) * wpb >= (1ull << 32)) {
+                set_error("gram4: more regions than 32-bit claims hold (gram_region / gram_region_small too small for this haystack)");
+                return DAAC_ERR_UNSUPPORTED;
+            }
+            // daac_last_kernel(): how many regions the launch has and how many of them are claimed from the counter, not owned
+            const uint64_t owned = ga.static_rounds == ~0u ? ga.nregions : std::min<uint64_t>(ga.nregions, static_cast<uint64_t>(ga.static_rounds) * blocks * wpb);
+            g_last_kernel = count_kernel_name(cp, " regions=" + std::to_string(ga.nregions) + " claims=" + std::to_string(ga.nregions - owned));
+        }
         // more than ~1 % of the (K+1)-grams are trie prefixes: some lane of the wave hits on nearly every position
         ga.dense = OPT(gram_dense) >= 0 ? OPT(gram_dense) != 0 : cp.n_deep * 100 > cp.C * cp.C * cp.C * (cp.K == 3 ? cp.C : 1);
         // gram4: tail records from the hit record on pay on text made of dictionary words (+20 %) and cost 3-4 % elsewhere; unless
         // the option decides, every workgroup samples the haystack at its start and runs the variant the text calls for
         const int64_t tail_opt = OPT(gram_tail);
+        // the call's scratch: [gram4's counters: {claims, count, workgroups done} of the scan, at +64 those of the halo's scan | the walker slabs].
+        // The counters live here and not in the handle: two calls on one handle (other streams, other threads) must not share them.  One
+        // clear serves the claim counter and the count (until round 14 the same one stream operation cleared d_res).
+        constexpr size_t kWqHead = 256;
         void *wq = nullptr;
-        HIP_TRY(dev_malloc(&wq, static_cast<size_t>(blocks) * wpb * ga.wq_slab * cp.wq_entry, stream));
-        ga.wq = static_cast<uint2 *>(wq);
+        HIP_TRY(dev_malloc(&wq, kWqHead + static_cast<size_t>(blocks) * wpb * ga.wq_slab * cp.wq_entry, stream));
+        ga.wq = reinterpret_cast<uint2 *>(static_cast<char *>(wq) + kWqHead);
+        ga.claim = static_cast<unsigned long long *>(wq);
+        if (g4_launch) {
+            const hipError_t ce = hipMemsetAsync(wq, 0, 128, stream);
+            if (ce != hipSuccess) { dev_free(wq, stream); HIP_TRY(ce); }
+        }
         ga.sel_want = tail_opt < 0 ? ((len - begin) >= (1ull << 20) ? 2u : 0u) : tail_opt > 0 ? 1u : 0u;
         auto launch_count = [&](const GramArgs &g, uint32_t nblocks) -> hipError_t {
             switch (cp.kernel) {
@@ -584,10 +635,13 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
         DevBuf halo_res;
         if (le == hipSuccess && from != begin) {   // what lies wholly inside the halo, counted the same way (ends from `from` as well)
             le = halo_res.alloc(3 * sizeof(unsigned long long), stream);
-            if (le == hipSuccess) le = hipMemsetAsync(halo_res.p, 0, 3 * sizeof(unsigned long long), stream);
+            if (le == hipSuccess && !g4_launch) le = hipMemsetAsync(halo_res.p, 0, 3 * sizeof(unsigned long long), stream);
             GramArgs gh = ga;
             gh.vlen = ga.lead + (begin - from);
             gh.nregions = (gh.vlen + gh.region_bytes - 1) / gh.region_bytes;   // (one: a halo is shorter than any region)
+            gh.nlarge = gh.nregions;
+            gh.static_rounds = ~0u;
+            gh.claim = ga.claim + 8;
             gh.result = static_cast<unsigned long long *>(halo_res.p);
             gh.sel_want = 0;
             if (le == hipSuccess) le = launch_count(gh, 1);   // (the first workgroup's slab of the walker queue: the scan before has drained it)

@@ -123,6 +123,11 @@ struct GramArgs {
     uint32_t dense;              // B hits are frequent: queue them position by position without testing the group first
     const uint32_t *sel;         // (unused)
     uint32_t sel_want;           // gram3: 0 = plain records, 1 = tail records from the hit record on, 2 = decided by the kernel's density probe
+    // gram4 only (gram4_claims.hpp): regions [0, nlarge) are region_bytes long, [nlarge, nregions) region_small; the others: nlarge = nregions
+    uint64_t region_small;
+    uint64_t nlarge;
+    unsigned long long *claim;   // gram4 only: {regions claimed beyond the static rounds, count, workgroups done}, all zero at launch
+    uint32_t static_rounds;      // gram4 only: a wave's first static_rounds regions are wave + k * nwaves (>= 1; ~0: all of them), the rest it claims
 };
 
 hipError_t launch_gram_scan(const GramDev &dev, const GramArgs &a, uint32_t blocks, uint32_t threads, hipStream_t stream);

@@ -47,6 +47,10 @@
 // entries are LDS addresses of byte p - 3 (`derive` adds no base and subtracts no 3).  (d) the count sum is v_and_b32 and two v_bcnt_u32_b32 onto the
 // region's count.  (e) the probe's pass mask is the two compares' masks or-ed on the scalar unit.  SQ_INSTS_VALU 18.51 -> 17.36 per byte and lane
 // (profiles/r11_gram4_*.txt).
+// Round 14: outside the step loop (profiles/r14_gram4_edges.txt: the waves of a launch ended 500 us apart).  The haystack's end is cut into small
+// regions (gram4_claims.hpp); a wave's first regions are static — whole rounds of the launch's waves —, the rest it claims from a counter in the
+// call's scratch; the launch's last workgroup stores the result, so one clear serves counter and count; the TAIL body asks for a region's first
+// text where the region before it ends; g4_copy keeps four loads in flight.  cfg3 2.375 -> 2.323 ms per 4 GiB.
 // Roofline: HBM bytes of haystack (1 B read per byte); integer/bit work only, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -55,6 +59,7 @@
 #include <utility>
 
 #include "device_tables.hpp"
+#include "gram4_claims.hpp"
 #include "gram4_filter.hpp"
 #include "gram4_index.hpp"
 
@@ -127,9 +132,18 @@ __device__ __forceinline__ unsigned long long g4_wave_sum(unsigned long long v) 
 __device__ __forceinline__ void g4_copy(void *dst, const void *src, uint32_t bytes) {
     const uint4 *s = reinterpret_cast<const uint4 *>(src);
     uint4 *d = reinterpret_cast<uint4 *>(dst);
-    for (uint32_t i = threadIdx.x; i < bytes / 16; i += blockDim.x) d[i] = s[i];
+    const uint32_t n = bytes / 16, bd = blockDim.x;
+    uint32_t i = threadIdx.x;
+    for (; i + 3u * bd < n; i += 4u * bd) {   // four loads of a thread in flight before its first LDS store (M: one round trip, not five)
+        const uint4 v0 = s[i], v1 = s[i + bd], v2 = s[i + 2u * bd], v3 = s[i + 3u * bd];
+        d[i] = v0; d[i + bd] = v1; d[i + 2u * bd] = v2; d[i + 3u * bd] = v3;
+    }
+    for (; i < n; i += bd) d[i] = s[i];
 }
-__device__ __forceinline__ void g4_reduce(unsigned long long cnt, unsigned long long *scratch, unsigned long long *result) {
+// The launch's count goes through the call's own block `claim` = {claims, count, workgroups done}, zero at launch (one clear for the claim
+// counter and the count): every workgroup adds its count to claim[1], and the one that finishes last STORES the sum and two zeros to
+// `result` — the caller's three words need no clear of their own in front of the launch.
+__device__ __forceinline__ void g4_reduce(unsigned long long cnt, unsigned long long *scratch, unsigned long long *claim, unsigned long long *result) {
     const unsigned long long c = g4_wave_sum(cnt);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -138,7 +152,56 @@ __device__ __forceinline__ void g4_reduce(unsigned long long cnt, unsigned long 
     if (threadIdx.x == 0) {
         unsigned long long r0 = 0;
         for (int w = 0; w < static_cast<int>((blockDim.x + 63) >> 6); ++w) r0 += scratch[w];
-        if (r0) atomicAdd(result, r0);
+        if (r0) atomicAdd(claim + 1, r0);
+        __threadfence();   // the count is added before this workgroup counts as done
+        if (atomicAdd(claim + 2, 1ull) + 1ull == gridDim.x) {
+            __threadfence();
+            result[0] = atomicAdd(claim + 1, 0ull);
+            result[1] = 0;
+            result[2] = 0;
+        }
+    }
+}
+// 16 bytes of text at virtual position v (a multiple of 16): what lies before the haystack's first byte or past its end reads as the unused byte
+__device__ __forceinline__ uint4 g4_load_chunk(const GramArgs &a, uint32_t unused_byte, uint64_t v) {
+    const uint32_t ub4 = unused_byte * 0x01010101u;
+    if (v >= a.vlen) return uint4{ub4, ub4, ub4, ub4};
+    const g4_u32x4_t q = __builtin_nontemporal_load(reinterpret_cast<const g4_u32x4_t *>(a.hay_al + v));
+    uint4 r{q.x, q.y, q.z, q.w};
+    if (v < a.lead || v + 16 > a.vlen) {  // first / last chunk of the haystack only
+        uint32_t w[4] = {r.x, r.y, r.z, r.w};
+        for (int b = 0; b < 16; ++b) {
+            const uint64_t p = v + b;
+            if (p < a.lead || p >= a.vlen) w[b >> 2] = (w[b >> 2] & ~(0xffu << (8 * (b & 3)))) | (unused_byte << (8 * (b & 3)));
+        }
+        r = uint4{w[0], w[1], w[2], w[3]};
+    }
+    return r;
+}
+// The text of the step at rbase + off of a region of rlen bytes, for the two fetches a region begins with (off = 0 and one step) where they
+// are asked for ahead of the region (gram4_body's AHEAD).  Same values as gram4_body's `fetch` (its interior form where that applies:
+// unconditional loads that nothing has to wait for here).
+template <int Q>
+__device__ __forceinline__ void g4_fetch_ahead(const GramArgs &a, uint32_t unused_byte, uint64_t rbase, uint32_t rlen, uint32_t off, uint4 (&out)[Q]) {
+    constexpr uint32_t P = 16u * Q, SB = 64u * P;
+    const uint32_t lane = threadIdx.x & 63, ub4 = unused_byte * 0x01010101u;
+    const uint32_t fast_lo = rbase < 16u ? SB : 0u, fast_hi = rlen & ~(SB - 1u);
+    if (off >= fast_lo && off < fast_hi) {
+        const uint8_t *__restrict__ base = a.hay_al + rbase + off;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const g4_u32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const g4_u32x4_t *>(base + lane * P + 16u * q));
+            out[q] = uint4{t.x, t.y, t.z, t.w};
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) out[q] = uint4{ub4, ub4, ub4, ub4};
+    if (off < rlen) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) out[q] = g4_load_chunk(a, unused_byte, rbase + off + lane * P + 16u * q);
+    } else if (lane == 0 && off < rlen + SB) {
+        out[0] = g4_load_chunk(a, unused_byte, rbase + off);
     }
 }
 
@@ -206,20 +269,7 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
     unsigned long long tot_cnt = 0;
     uint32_t cnt32 = 0;  // matches of the current region (a region is far too short to overflow 32 bits)
 
-    auto load_chunk = [&](uint64_t v) -> uint4 {
-        if (v >= a.vlen) return uint4{ub4, ub4, ub4, ub4};
-        const g4_u32x4_t q = __builtin_nontemporal_load(reinterpret_cast<const g4_u32x4_t *>(hay + v));
-        uint4 r{q.x, q.y, q.z, q.w};
-        if (v < a.lead || v + 16 > a.vlen) {  // first / last chunk of the haystack only
-            uint32_t w[4] = {r.x, r.y, r.z, r.w};
-            for (int b = 0; b < 16; ++b) {
-                const uint64_t p = v + b;
-                if (p < a.lead || p >= a.vlen) w[b >> 2] = (w[b >> 2] & ~(0xffu << (8 * (b & 3)))) | (g.unused_byte << (8 * (b & 3)));
-            }
-            r = uint4{w[0], w[1], w[2], w[3]};
-        }
-        return r;
-    };
+    auto load_chunk = [&](uint64_t v) -> uint4 { return g4_load_chunk(a, g.unused_byte, v); };
     auto raw_at = [&](uint64_t p) -> uint32_t { return (p >= a.lead && p < a.vlen) ? hay[p] : g.unused_byte; };
     auto read_ahead = [&](uint64_t v) -> unsigned long long {
         unsigned long long x;
@@ -662,13 +712,52 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         }
     };
 
-    uint64_t region = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave_in_wg;
-    while (region < a.nregions) {
-      slab_hi = static_cast<uint32_t>((region * a.region_bytes) >> 31);
+    // Regions are claimed, not owned (round 14).  A wave's first a.static_rounds regions are its own number in the launch plus multiples of
+    // nwaves — no wave waits for an atomic before its first byte —; every further one is the next value of the call's counter
+    // a.claim[0], which starts at 0 and stands for region static_rounds * nwaves: one relaxed agent-scope add by lane 0, broadcast to the
+    // wave.  (The host makes every whole round of large regions static: all waves of a launch start within 2 us of each other, and 4 096
+    // adds to one address at once queue for 60 us at the L2 — measured, profiles/r14_gram4_edges.txt; by the last static round the waves
+    // are hundreds of microseconds apart.)  The claim for the region after this one goes out at this region's start, behind its first text
+    // fetches, and comes back with them.  A claim index is turned into bytes by g4_claim_region: large regions first, small ones at the
+    // haystack's end, where they even out the finish times of the waves.
+    // INVARIANT the epoch logic below rests on: the regions of a wave ascend.  Its static indices ascend and lie below static_rounds * nwaves,
+    // every claim is at least that, and the counter only grows, so a later claim of the same wave is larger than an earlier one; g4_claim_region is monotone in
+    // the index.  A wave therefore never returns to an earlier 2 GiB epoch, and the slab is drained whenever the epoch changes.
+    // (Region indices, their number and the claims fit 32 bits — every wave claims once more than it scans, and the host refuses a launch
+    // whose regions + waves reach 2^32 —, so the low word of the 64-bit counter is the claim; the sizes go by their logarithms: fewer scalar registers live
+    // through the step loop than 64-bit indices and sizes took.)
+    const uint32_t nregions = static_cast<uint32_t>(a.nregions), nlarge = static_cast<uint32_t>(a.nlarge), nwaves32 = static_cast<uint32_t>(nwaves);
+    const uint32_t lg_large = static_cast<uint32_t>(__builtin_ctzll(a.region_bytes)), lg_small = static_cast<uint32_t>(__builtin_ctzll(a.region_small));
+    const uint32_t claim_base = nwaves32 * a.static_rounds;
+    uint32_t static_left = a.static_rounds - 1u;   // static regions of this wave behind the current one
+    auto claim_next = [&]() -> uint32_t {
+        unsigned long long c = 0;
+        if (lane == 0) c = __hip_atomic_fetch_add(a.claim, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return claim_base + __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(c));
+    };
+    auto region_of = [&](uint32_t r) -> G4Region { return g4_claim_region(r, lg_large, lg_small, nlarge); };
+    uint32_t region = blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
+    // pf0 / pf1: the text of the next two steps, the step loop's own registers.  AHEAD (the TAIL body at 32 positions per lane): a region
+    // finds its first two steps in them, asked for where the region before it ends (after the drain, if the epoch changes) and in front of
+    // the region's own dependent loads (the bytes before it, their M word).  Measured (profiles/r14_gram4_edges.txt): word soup -4 %; the
+    // FILT body +2 % on uniform text (102 VGPRs for 92), so it and the plain body ask at the region's start, as until round 14; at 16
+    // positions per lane the text held across a region's end would cost the 64-VGPR budget that lets two workgroups share a CU.
+    constexpr bool AHEAD = Q == 2 && TAIL;
+    uint4 pf0[Q], pf1[Q];
+    auto fetch_ahead = [&](uint32_t r) {
+        const G4Region rg = region_of(r);
+        const uint32_t len = static_cast<uint32_t>((rg.base + rg.size < a.vlen ? rg.base + rg.size : a.vlen) - rg.base);
+        g4_fetch_ahead<Q>(a, g.unused_byte, rg.base, len, 0u, pf0);
+        g4_fetch_ahead<Q>(a, g.unused_byte, rg.base, len, SB, pf1);
+    };
+    if constexpr (AHEAD) if (region < nregions) fetch_ahead(region);
+    while (region < nregions) {
+      slab_hi = static_cast<uint32_t>(region_of(region).base >> 31);
       epoch_base = static_cast<uint64_t>(slab_hi) << 31;
-      for (; region < a.nregions && static_cast<uint32_t>((region * a.region_bytes) >> 31) == slab_hi; region += nwaves) {
-        const uint64_t rbase = region * a.region_bytes;
-        const uint64_t rend = rbase + a.region_bytes < a.vlen ? rbase + a.region_bytes : a.vlen;
+      for (;;) {
+        const G4Region rg = region_of(region);
+        const uint64_t rbase = rg.base;
+        const uint64_t rend = rbase + rg.size < a.vlen ? rbase + rg.size : a.vlen;
         // classes of the K bytes before the region, oldest in the low byte; the four raw bytes before it
         uint32_t carry = 0, tail4 = 0;
 #pragma unroll
@@ -715,9 +804,12 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
                 out[0] = load_chunk(s0);
             }
         };
-        uint4 pf0[Q], pf1[Q];
-        fetch(0u, pf0);
-        fetch(SB, pf1);
+        if constexpr (!AHEAD) {
+            fetch(0u, pf0);
+            fetch(SB, pf1);
+        }
+        uint32_t region_next = region + nwaves32;
+        if (static_left != 0) --static_left; else region_next = claim_next();
         const uint32_t rbias = static_cast<uint32_t>(rbase - epoch_base) - (tb + 16u - 3u);   // posbias of the region's first step (the entry of a hit byte lies 3 below its address)
 
         for (uint32_t off = 0; off < rlen; off += SB) {
@@ -854,6 +946,9 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
         }
         tot_cnt += cnt32;  // per region: 32 bits cannot overflow within one
         cnt32 = 0;
+        region = region_next;
+        if (!(region < nregions && static_cast<uint32_t>(region_of(region).base >> 31) == slab_hi)) break;
+        if constexpr (AHEAD) fetch_ahead(region);
       }
       if (st_n + q_tail - q_head != 0) process_batch(st_n + q_tail - q_head);
       if (FILT && sb_n != 0) { survivors_ask(sb_n); sb_n = 0; }
@@ -862,8 +957,9 @@ __device__ __forceinline__ void gram4_body(const Gram4Dev &g, const GramArgs &a,
       drain();
       tot_cnt += cnt32;
       cnt32 = 0;
+      if constexpr (AHEAD) if (region < nregions) fetch_ahead(region);   // (the next epoch's first region)
     }
-    g4_reduce(tot_cnt, reinterpret_cast<unsigned long long *>(smem), a.result);
+    g4_reduce(tot_cnt, reinterpret_cast<unsigned long long *>(smem), a.claim, a.result);
 }
 
 // One kernel, the variants inside: the workgroup stages M, decides TAIL (a.sel_want: 0 / 1, or 2 = by its own density probe), stages the

@@ -198,7 +198,7 @@ void daac_free(void *p);
  * e.g. GRAM declines ranges of 32 GiB and more and automata whose tables do not fit LDS). */
 int daac_last_engine(void);
 /* The kernel family — and, for the `.count()` kernel, the launch shape the options in force gave it ("gram4 ppl=32 dir=0 waves=16 arith=1 filter=1
- * tail=auto") — that served the calling thread's last daac_scan_count* call (daac_scan_count_multi: shard 0's, as run by its device's worker).
+ * mph=1 regions=23552 claims=11264 tail=auto": regions of the launch, and how many of them its waves claim from the call's counter) — that served the calling thread's last daac_scan_count* call (daac_scan_count_multi: shard 0's, as run by its device's worker).
  * ABI 6; a diagnostic: the text is not a contract. */
 const char *daac_last_kernel(void);
 
@@ -822,7 +822,7 @@ void daac_stream_close(daac_stream *s);
  *   seg_bytes (0 = auto)        bytes of haystack per lane-segment of the segment scanners
  *   threads (1024), blocks_per_cu (0 = auto)   launch shape of the overlapping scanners
  *   lds_budget (98304), dense_depth (-1 = auto), rows_share_pct (45)   TIERED re-pack
- *   gram_lds_budget (161792), gram_region (0 = auto: 16384 for the first table set, 65536 for the second and PFX, 262144 from 2 GiB on; rounded down to a power of two >= 2048), gram_slab (4096), gram_dense (-1 = auto), gram_rank_in_lds (-1 = auto),
+ *   gram_lds_budget (161792), gram_region (0 = auto: 16384 for the first table set, 65536 for the second and PFX, 262144 from 2 GiB on; rounded down to a power of two >= 2048), gram_slab (4096), gram_region_small (0 = auto: 32768; gram4: bytes of the small regions the haystack's end is cut into, a power of two <= gram_region), gram_taper_split (-1 = auto; gram4: the byte the small regions begin at, rounded down to a whole region; past the end: none; expert knobs for tests and timing runs: a split in front of the launch's first whole round of large regions makes every wave claim at the start of the scan, and that many adds to one counter at once queue for tens of microseconds), gram_dense (-1 = auto), gram_rank_in_lds (-1 = auto),
  *   gram_ppl (0 = auto: 32 positions per lane and step for automata without short patterns, else 16)
  *   gram_version (0 = auto: `.count()` on the gram4 kernel over the renumbered second table set, count + checksum on the first where it applies;
  *                 1 = first table set only, 2 = gram2 kernels only, 4 (3: its name in ABI 4) = gram4 for `.count()` or an error), gram2_dpp (1: DPP wave shifts),
