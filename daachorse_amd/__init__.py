@@ -9,7 +9,7 @@ from . import _ffi
 from ._ffi import DaachorseError, last_engine, last_kernel, set_option
 from .bytewise import (DoubleArrayAhoCorasick, DoubleArrayAhoCorasickBuilder, Engine, Gap, Match, MatchKind, ScanMode,
                        MATCH_DTYPE, MATCH16_DTYPE, SLOT_COUNT_DTYPE, scan_count_multi,
-                       Split, Splitter, char_classes, split_batch, offsets_compose, bert_char_classes, wordpiece_tables,
+                       Split, Splitter, char_classes, split_batch, offsets_compose, bert_char_classes, o200k_char_classes, wordpiece_tables,
                        Norm, Normalizer, bert_normalizer, bert_normalizer_rules)
 from .charwise import CharwiseDoubleArrayAhoCorasick, CharwiseDoubleArrayAhoCorasickBuilder
 
@@ -18,5 +18,5 @@ _ffi.lib()  # fail loudly at import time if the extension is missing
 __all__ = ["DoubleArrayAhoCorasick", "DoubleArrayAhoCorasickBuilder", "CharwiseDoubleArrayAhoCorasick",
            "CharwiseDoubleArrayAhoCorasickBuilder", "Match", "MatchKind", "ScanMode", "Engine", "Gap",
            "DaachorseError", "set_option", "last_engine", "last_kernel", "MATCH_DTYPE", "MATCH16_DTYPE", "SLOT_COUNT_DTYPE", "scan_count_multi",
-           "Split", "Splitter", "char_classes", "split_batch", "offsets_compose", "bert_char_classes",
+           "Split", "Splitter", "char_classes", "split_batch", "offsets_compose", "bert_char_classes", "o200k_char_classes",
            "wordpiece_tables", "Norm", "Normalizer", "bert_normalizer", "bert_normalizer_rules"]

@@ -56,6 +56,7 @@ class Split(enum.IntEnum):
     Cl100k = 3       # tiktoken's cl100k_base pattern (2 is reserved)
     Llama3 = 4       # the pattern of Llama-3's tokenizer.json
     Bert = 6         # BERT's pre-tokenizer: whitespace runs, every punctuation character alone, runs of everything else (5 is refused)
+    O200k = 8        # tiktoken's o200k_base pattern: case phases, marks, contractions as suffixes (7 is refused)
 
 
 class Match:
@@ -1058,13 +1059,43 @@ def bert_char_classes():
     return _bert_char_classes
 
 
+_o200k_char_classes = None
+
+
+def o200k_char_classes():
+    """The classes of the code points from U+0080 on under which Split.O200k gives the words of tiktoken's o200k_base pattern: rows
+    {first, last, cls} as char_classes() has them, with cls 1 = a caseless letter (general categories Lm, Lo), 2 = N (N*), 3 = S (the
+    White_Space code points of char_classes()), 4 = an upper letter (Lu, Lt), 5 = a lower letter (Ll) and 6 = a mark (M*); every other
+    code point is O.  The categories are the standard library's (Unicode `unicodedata.unidata_version`).  Computed once and cached
+    (read-only)."""
+    global _o200k_char_classes
+    if _o200k_char_classes is None:
+        import unicodedata
+        white = frozenset(_WHITE_SPACE)
+        cls_of = {"Lu": 4, "Lt": 4, "Ll": 5, "Lm": 1, "Lo": 1, "Mn": 6, "Mc": 6, "Me": 6, "Nd": 2, "Nl": 2, "No": 2}
+        rows, first, cur = [], 0, 0
+        for cp in range(0x80, 0x110001):
+            c = 0
+            if cp <= 0x10FFFF:
+                c = 3 if cp in white else cls_of.get(unicodedata.category(chr(cp)), 0)
+            if c != cur:
+                if cur:
+                    rows.append((first, cp - 1, cur))
+                first, cur = cp, c
+        a = np.array(rows, dtype=np.uint32).reshape(len(rows), 3)
+        a.setflags(write=False)
+        _o200k_char_classes = a
+    return _o200k_char_classes
+
+
 class Splitter:
     """daac_splitter: a split rule and the classes of the code points from U+0080 on (`classes`: rows {first, last, cls} as
-    char_classes() gives them, the default; sorted and disjoint, cls 1 = L, 2 = N, 3 = S).  Below U+0080 the classes are fixed."""
+    char_classes() gives them, the default (o200k_char_classes() under Split.O200k); sorted and disjoint, cls 1 = L, 2 = N, 3 = S, and
+    under Split.O200k also 4 = upper, 5 = lower, 6 = mark, with 1 a caseless letter).  Below U+0080 the classes are fixed."""
 
     def __init__(self, rule=Split.Gpt2, classes=None):
         self._h = None
-        a = char_classes() if classes is None else np.asarray(classes)
+        a = (o200k_char_classes() if rule == Split.O200k else char_classes()) if classes is None else np.asarray(classes)
         if a.size and (a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xFFFFFFFF):
             raise DaachorseError(1, "classes must be rows {first, last, cls} of integers in 0 .. 0xFFFFFFFF")
         a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 3)
@@ -1151,7 +1182,7 @@ _default_splitters = {}
 
 
 def _default_splitter(rule):
-    rule = Split(rule) if rule in (0, 1, 3, 4, 6) else rule
+    rule = Split(rule) if rule in (0, 1, 3, 4, 6, 8) else rule
     sp = _default_splitters.get(rule)
     if sp is None:
         sp = _default_splitters[rule] = Splitter(rule, bert_char_classes() if rule == Split.Bert else None)
@@ -1185,7 +1216,8 @@ def wordpiece_tables(vocab, prefix="##"):
 
 
 def split_batch(docs, rule=Split.Gpt2, stream=None, device=False):
-    """Splitter(rule).split_batch(docs) on a cached splitter with the default classes (char_classes())"""
+    """Splitter(rule).split_batch(docs) on a cached splitter with the rule's default classes (char_classes(); Split.Bert:
+    bert_char_classes(); Split.O200k: o200k_char_classes())"""
     return _default_splitter(rule).split_batch(docs, stream=stream, device=device)
 
 

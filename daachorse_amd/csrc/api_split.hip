@@ -11,7 +11,7 @@
 struct daac_splitter {
     int rule = DAAC_SPLIT_GPT2;
     std::vector<uint16_t> stage1;   // kSplitStage1 block numbers
-    std::vector<uint8_t> stage2;    // blocks of kSplitBlockBytes; block 0 is all O
+    std::vector<uint8_t> stage2;    // blocks of kSplitBlockBytes (DAAC_SPLIT_O200K: kSplitBlockBytes4, four bits a code point); block 0 is all O
     std::mutex mu;
     std::map<int, void *> dev;      // per device: stage1, then stage2 at byte 2 * kSplitStage1
 };
@@ -39,7 +39,7 @@ daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
     return DAAC_OK;
 }
 
-const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : rule == DAAC_SPLIT_BERT ? "bert" : "whitespace"; }
+const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : rule == DAAC_SPLIT_BERT ? "bert" : rule == DAAC_SPLIT_O200K ? "o200k" : "whitespace"; }
 bool rule_scans(int rule) { return rule == DAAC_SPLIT_CL100K || rule == DAAC_SPLIT_LLAMA3; }
 
 // Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
@@ -92,15 +92,17 @@ daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t 
     a.n_docs = n;
     a.rule = sp->rule;
     a.tiles = (total + daac::kSplitTile - 1) / daac::kSplitTile;
-    // the scratch: the tile counts, their sum, the sum's scratch, the masks, the marks; for a rule with scans three words a tile more
+    // the scratch: the tile counts, their sum, the sum's scratch, the masks, the marks; for a rule with scans three words a tile more, for
+    // DAAC_SPLIT_O200K a 64-bit map a tile on top of them (in front of the masks: aligned)
     const uint64_t n_mask = a.tiles * (daac::kSplitTile / 64), n_mark = a.tiles * (daac::kSplitTile / 32) + 1, n_scan = exclusive_scan_scratch(a.tiles);
-    const uint64_t n_carry = rule_scans(sp->rule) ? 3 * a.tiles : 0;
+    const bool o200k = sp->rule == DAAC_SPLIT_O200K;
+    const uint64_t n_carry = rule_scans(sp->rule) || o200k ? 3 * a.tiles : 0, n_map = o200k ? a.tiles : 0;
     DevBuf work;
-    HIP_TRY(work.alloc((a.tiles + 1 + n_scan + n_mask) * sizeof(unsigned long long) + (n_mark + n_carry) * sizeof(uint32_t), stream));
+    HIP_TRY(work.alloc((a.tiles + 1 + n_scan + n_map + n_mask) * sizeof(unsigned long long) + (n_mark + n_carry) * sizeof(uint32_t), stream));
     a.counts = static_cast<unsigned long long *>(work.p);
     unsigned long long *sum = a.counts + a.tiles, *scan_scratch = sum + 1;
     a.n_words = sum;
-    a.masks = scan_scratch + n_scan;
+    a.masks = scan_scratch + n_scan + n_map;
     a.marks = reinterpret_cast<uint32_t *>(a.masks + n_mask);
     HIP_TRY(hipMemsetAsync(a.marks, 0, n_mark * sizeof(uint32_t), stream));
     HIP_TRY(daac::launch_split_marks(a, stream));
@@ -108,7 +110,8 @@ daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t 
         a.tile_sum = a.marks + n_mark;
         a.carry_f = a.tile_sum + a.tiles;
         a.carry_b = a.carry_f + a.tiles;
-        HIP_TRY(daac::launch_split_flags_scanned(a, stream));
+        if (o200k) HIP_TRY(daac::launch_split_flags_o200k(daac::SplitO200kArgs{a, scan_scratch + n_scan}, stream));
+        else HIP_TRY(daac::launch_split_flags_scanned(a, stream));
     } else {
         HIP_TRY(daac::launch_split_flags(a, stream));
     }
@@ -140,8 +143,9 @@ extern "C" {
 daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t n_ranges, daac_splitter **out) {
     if (!out) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
     *out = nullptr;
-    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2 && rule != DAAC_SPLIT_CL100K && rule != DAAC_SPLIT_LLAMA3 && rule != DAAC_SPLIT_BERT) {
-        set_error("rule is none of DAAC_SPLIT_WHITESPACE, DAAC_SPLIT_GPT2, DAAC_SPLIT_CL100K, DAAC_SPLIT_LLAMA3 and DAAC_SPLIT_BERT");
+    if (rule != DAAC_SPLIT_WHITESPACE && rule != DAAC_SPLIT_GPT2 && rule != DAAC_SPLIT_CL100K && rule != DAAC_SPLIT_LLAMA3 && rule != DAAC_SPLIT_BERT &&
+        rule != DAAC_SPLIT_O200K) {
+        set_error("rule is none of DAAC_SPLIT_WHITESPACE, DAAC_SPLIT_GPT2, DAAC_SPLIT_CL100K, DAAC_SPLIT_LLAMA3, DAAC_SPLIT_BERT and DAAC_SPLIT_O200K");
         return DAAC_ERR_INVALID_ARGUMENT;
     }
     if (n_ranges && !ranges) { set_error("ranges is NULL with n_ranges = " + std::to_string(n_ranges)); return DAAC_ERR_INVALID_ARGUMENT; }
@@ -151,14 +155,18 @@ daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t
         if (r.last < r.first) { set_error(at + ": last < first"); return DAAC_ERR_INVALID_ARGUMENT; }
         if (r.first < 0x80u) { set_error(at + ": first is below U+0080 (the ASCII classes are fixed)"); return DAAC_ERR_INVALID_ARGUMENT; }
         if (r.last > 0x10FFFFu) { set_error(at + ": last is above U+10FFFF"); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (r.cls < 1u || r.cls > 3u) { set_error(at + ": cls is not 1 (L), 2 (N) or 3 (S)"); return DAAC_ERR_INVALID_ARGUMENT; }
+        if (r.cls < 1u || r.cls > (rule == DAAC_SPLIT_O200K ? 6u : 3u)) {
+            set_error(at + (rule == DAAC_SPLIT_O200K ? ": cls is not 1 (caseless L), 2 (N), 3 (S), 4 (upper), 5 (lower) or 6 (mark)" : ": cls is not 1 (L), 2 (N) or 3 (S)"));
+            return DAAC_ERR_INVALID_ARGUMENT;
+        }
         if (i && r.first <= ranges[i - 1].last) { set_error(at + ": the ranges are not sorted and disjoint"); return DAAC_ERR_INVALID_ARGUMENT; }
     }
-    // the two-stage table: equal blocks of 256 code points are stored once
+    // the two-stage table: equal blocks of 256 code points are stored once; two bits a code point, four under DAAC_SPLIT_O200K
+    const uint32_t bits = rule == DAAC_SPLIT_O200K ? 4u : 2u, per_byte = 8u / bits, block_bytes = 256u / per_byte;
     std::unique_ptr<daac_splitter> sp(new daac_splitter);
     sp->rule = rule;
     sp->stage1.assign(daac::kSplitStage1, 0);
-    sp->stage2.assign(daac::kSplitBlockBytes, 0);
+    sp->stage2.assign(block_bytes, 0);
     std::map<std::vector<uint8_t>, uint16_t> seen;
     seen.emplace(sp->stage2, 0);
     size_t r = 0;
@@ -166,10 +174,10 @@ daac_status daac_splitter_create(int rule, const daac_char_range *ranges, size_t
         const uint32_t lo_cp = hi << 8, hi_cp = lo_cp + 255u;
         while (r < n_ranges && ranges[r].last < lo_cp) ++r;
         if (r == n_ranges || ranges[r].first > hi_cp) continue;   // all O: block 0
-        std::vector<uint8_t> blk(daac::kSplitBlockBytes, 0);
+        std::vector<uint8_t> blk(block_bytes, 0);
         for (size_t j = r; j < n_ranges && ranges[j].first <= hi_cp; ++j)
             for (uint32_t cp = std::max(ranges[j].first, lo_cp); cp <= std::min(ranges[j].last, hi_cp); ++cp)
-                blk[(cp & 255u) >> 2] = static_cast<uint8_t>(blk[(cp & 255u) >> 2] | ranges[j].cls << (2u * (cp & 3u)));
+                blk[(cp & 255u) / per_byte] = static_cast<uint8_t>(blk[(cp & 255u) / per_byte] | ranges[j].cls << (bits * (cp % per_byte)));
         auto it = seen.find(blk);
         if (it == seen.end()) {
             it = seen.emplace(blk, static_cast<uint16_t>(seen.size())).first;   // (at most kSplitStage1 blocks: 16 bits hold the number)
@@ -292,7 +300,7 @@ daac_status daac_split_words_space(daac_splitter *sp, const uint8_t *hay, const 
     HIP_TRY(dev_malloc(&flags, n_words, stream));
     std::unique_ptr<void, std::function<void(void *)>> g(flags, [stream](void *q) { dev_free(q, stream); });
     HIP_TRY(daac::launch_split_words_space(tab, dev_hay, reinterpret_cast<const unsigned long long *>(dev_word_offsets), n_words, ends[0], ends[1],
-                                           static_cast<uint8_t *>(flags), stream));
+                                           static_cast<uint8_t *>(flags), stream, sp->rule == DAAC_SPLIT_O200K));
     HIP_TRY(hipStreamSynchronize(stream));
     *dev_flags = static_cast<uint8_t *>(g.release());
     return DAAC_OK;

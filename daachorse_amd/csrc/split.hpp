@@ -9,6 +9,7 @@
 // DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a position that depend on runs of any length (a digit's index in its
 // run mod 3, newlines behind punctuation, a newline farther on in a whitespace run, a whitespace run that reaches the document's end):
 // segmented scans over the batch, two forwards and two backwards, in three passes that never wait for one another (split_kernels.hip).
+// DAAC_SPLIT_O200K has the same three passes with states of its own: forwards one automaton of 13 states, backwards two bits.
 //
 // Positions p count from offsets[0]: 0 <= p < total = offsets[n] - offsets[0].  The scratch of a call:
 //   marks   one bit per position 0 .. total: a non-empty document starts here (bit `total`: the text ends here); set with atomicOr
@@ -36,6 +37,10 @@ constexpr uint32_t kSplitStage1 = 0x1100;   // entries of the class table's firs
 constexpr uint32_t kSplitBlockBytes = 64;   // a second-stage block: 256 code points, two bits each
 
 enum : uint32_t { kSplitO = 0, kSplitL = 1, kSplitN = 2, kSplitS = 3 };
+// DAAC_SPLIT_O200K: three classes more, and L is then a caseless letter.  Its table has four bits per code point in blocks of
+// kSplitBlockBytes4: (stage2[stage1[cp >> 8] * 128 + ((cp & 255) >> 1)] >> 4 * (cp & 1)) & 15.
+enum : uint32_t { kSplitUp = 4, kSplitLow = 5, kSplitMark = 6 };
+constexpr uint32_t kSplitBlockBytes4 = 128;
 constexpr uint32_t kSplitCarryLanes = 1024;   // lanes of the one workgroup that resolves the carries across tiles
 
 // A scan state is a function of the positions in front of (forwards) or behind (backwards) a position; a position either keeps the
@@ -79,7 +84,16 @@ struct SplitArgs {
     unsigned long long *doc_words;        // n_docs + 1
 };
 
+// DAAC_SPLIT_O200K: the arguments of its own passes.  Scratch per tile, 20 bytes: tile_map (what the tile does to the forward state, a
+// packed map of 16 states), a.tile_sum (what it does to the two backward bits), a.carry_f (the forward state in front of the tile) and
+// a.carry_b (the backward bits behind it).  split_kernels.hip has the states.
+struct SplitO200kArgs {
+    SplitArgs a;
+    unsigned long long *tile_map;   // tiles entries
+};
+
 #ifndef DAAC_SPLIT_HOST
+hipError_t launch_split_flags_o200k(const SplitO200kArgs &a, hipStream_t stream);   // tile_map and tile_sum, the carries, then masks and counts
 hipError_t launch_split_marks(const SplitArgs &a, hipStream_t stream);     // marks (zeroed by the caller)
 hipError_t launch_split_flags(const SplitArgs &a, hipStream_t stream);     // masks and counts
 // DAAC_SPLIT_CL100K / DAAC_SPLIT_LLAMA3: tile_sum, then carry_f and carry_b, then masks and counts
@@ -91,9 +105,9 @@ hipError_t launch_offsets_compose(const unsigned long long *inner, const unsigne
 hipError_t launch_spans_rebase(unsigned long long *spans, const unsigned long long *tok_offsets, const unsigned long long *word_offsets,
                                const unsigned long long *doc_words, const unsigned long long *doc_off, uint64_t n_words, uint64_t n_docs, hipStream_t stream);
 // flags[w] = 1 iff the word [word_offsets[w], word_offsets[w+1]) of `text` (the byte that offset 0 names) is not empty and its first unit is
-// of class S; a word that is not inside [lo, hi) gets 0 and none of its bytes is read: one lane per word
+// of class S; a word that is not inside [lo, hi) gets 0 and none of its bytes is read: one lane per word.  o200k: tab is DAAC_SPLIT_O200K's
 hipError_t launch_split_words_space(const SplitTable &tab, const uint8_t *text, const unsigned long long *word_offsets, uint64_t n_words, uint64_t lo, uint64_t hi,
-                                    uint8_t *flags, hipStream_t stream);
+                                    uint8_t *flags, hipStream_t stream, bool o200k = false);
 #endif
 
 }  // namespace daac

@@ -582,7 +582,9 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  *     leaves the document.
  *   Classes: L (letter), N (number), S (whitespace) and O (everything else).  Below U+0080 they are fixed: A-Z a-z are L, 0-9 are N,
  *     0x09..0x0D and 0x20 are S, the rest is O.  From U+0080 on they come from the splitter's table of sorted, disjoint ranges
- *     {first, last, cls}, cls in {1 = L, 2 = N, 3 = S}; a code point in no range is O.
+ *     {first, last, cls}, cls in {1 = L, 2 = N, 3 = S}; a code point in no range is O.  Under DAAC_SPLIT_O200K alone cls may also be
+ *     4 (an upper letter: general categories Lu, Lt), 5 (a lower letter: Ll) or 6 (a mark: M*); 1 then means a caseless letter (Lm, Lo),
+ *     and below U+0080 A-Z are upper and a-z lower.  A splitter of any other rule refuses cls above 3.
  *   Rules: each partitions every document — its words are contiguous and cover it, nothing is dropped.
  *     DAAC_SPLIT_WHITESPACE: the words are the matches of \s+|\S+: maximal runs of S units and maximal runs of other units.
  *     DAAC_SPLIT_GPT2: the words are the successive matches of
@@ -610,6 +612,21 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  *     than 0x09..0x0D are O here and become words of their own where `tokenizers` leaves them inside words: BERT's normalizer
  *     (clean_text) removes them before the split, which is the caller's job as lower-casing and accent stripping are.  Ill-formed UTF-8
  *     bytes are O units, as everywhere in the splitter.  The rule looks one unit back and launches no scan.
+ *     DAAC_SPLIT_O200K: the words are the successive matches of tiktoken's o200k_base pattern,
+ *       [^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *       |[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *       |\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ *     with \p{Lu}\p{Lt} = class 4, \p{Ll} = 5, \p{Lm}\p{Lo} = 1, \p{M} = 6, \p{L} = 1, 4 and 5, \p{N} = N, \s = S; bytes, folding and
+ *     `(?i:)` as in the two rules above (U+017F matches s where the table has it as a letter of any case).  The quantifiers are greedy
+ *     and give back.  How it differs from those two rules: (1) a word body is upper-or-caseless units (4, 1, 6) then at least one
+ *     lower-or-caseless unit (5, 1, 6), or failing that at least one of the first kind then any of the second, so HTMLParser is one
+ *     word, XMLHttpRequest is XMLHttp|Request, and a run of upper letters that reaches a non-letter backs off to the last caseless unit
+ *     or mark in front of it (AB<Lo>CD -> AB<Lo>|CD, but AB<Lo>CDe is one word); (2) a mark is not \p{L}: it can be the optional
+ *     prefix and belongs to the punctuation alternative, and it is also word body, so !<M>abc is one word while !!<M>abc is
+ *     !!<M>|abc; (3) a contraction is a suffix of the word in front of it (don't and DON'T are one word, 1's is 1|'s), not a word of
+ *     its own; (4) the punctuation alternative's trailer also takes / (!\n/! -> !\n/|!, !/! is one word); (5) numbers, newlines and
+ *     whitespace are Llama-3's.  The value 7 is refused.  (o200k_base: GPT-4o and the vocabularies trained with its pattern; the Python
+ *     package's o200k_char_classes() has the table.)
  *   The kernels evaluate an equivalent local form — whether a word starts at a unit follows from three units in front of it and one
  *     behind it (split_kernels.hip states it) — so the unit of parallelism is the byte.  A word start is always the first byte of a unit.
  *     DAAC_SPLIT_CL100K and DAAC_SPLIT_LLAMA3 read four more bits of a unit that depend on runs of any length (a digit's index in its
@@ -617,9 +634,13 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  *     end): segmented scans over the batch that start again at every document, two forwards and two backwards, in two more passes —
  *     per-tile summaries, then one workgroup that resolves the carries across tiles.  No workgroup waits for another, and the work at a
  *     byte does not depend on the length of the run it lies in.  Scratch for them: 12 bytes per 1024 bytes of text.
- * daac_splitter_create builds a two-stage class table on the host from the ranges (n_ranges = 0: every code point from U+0080 on is O);
+ *     DAAC_SPLIT_O200K runs the same three passes with kernels of its own: forwards one automaton of 13 states (the kind of match a
+ *     unit lies in, the case phase of a word body, a digit's index mod 3) whose transitions compose as packed maps, backwards two bits
+ *     (a newline farther on in a whitespace run; a run of upper letters that ends at a non-letter).  Scratch: 20 bytes per 1024 bytes.
+ * daac_splitter_create builds a two-stage class table on the host from the ranges (n_ranges = 0: every code point from U+0080 on is O),
+ * two bits a code point, four under DAAC_SPLIT_O200K;
  * the table is uploaded per device on first use.  Status 1: a NULL out, an unknown rule, ranges that are unsorted, overlapping, have
- * last < first, first < 0x80, last > 0x10FFFF or cls outside 1..3.
+ * last < first, first < 0x80, last > 0x10FFFF or cls outside 1..3 (1..6 under DAAC_SPLIT_O200K).
  * daac_split_batch: *dev_word_offsets holds *n_words + 1 u64 positions in hay — absolute, entry 0 is offsets[0], the last entry is
  * offsets[n]; *dev_doc_words holds n + 1 u64: document i's words are [doc_words[i], doc_words[i+1]), an empty document has none,
  * doc_words[n] == n_words.  Both are device memory, released with daac_device_free.  The call returns after the stream has finished.
@@ -627,7 +648,7 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
  * Decided before a device is touched — status 1: a NULL sp, dev_word_offsets, dev_doc_words or n_words; the batch offset rules of
  * daac_scan_count_batch (host offsets; device offsets are validated as that call validates them, with one read-back).  Status 2: a
  * word list above the process-wide option max_result_bytes (8 bytes a word), answered before it is allocated.  A host haystack is
- * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=.." (rule=whitespace, gpt2, cl100k, llama3 or bert).
+ * copied to the device once.  daac_last_kernel() says "split rule=.. docs=.. bytes=.. words=.." (rule=whitespace, gpt2, cl100k, llama3, bert or o200k).
  * Method: one lane per document marks its first byte in a bit array; a workgroup stages a tile of 1024 bytes, 12 in front and 7 behind
  * in LDS and each lane decides its byte; a wave ballot makes a 64-bit mask word; the per-tile popcounts are summed (one read-back of
  * the total) and a second pass writes every start at its rank.  Integer work only: the result is a function of the input alone. */
@@ -638,7 +659,9 @@ typedef enum {
     DAAC_SPLIT_CL100K = 3,
     DAAC_SPLIT_LLAMA3 = 4,
     /* 5 is refused, as it has been since the rules above were added */
-    DAAC_SPLIT_BERT = 6
+    DAAC_SPLIT_BERT = 6,
+    /* 7 is refused */
+    DAAC_SPLIT_O200K = 8
 } daac_split_rule;
 typedef struct { uint32_t first, last, cls; } daac_char_range;
 typedef struct daac_splitter daac_splitter;

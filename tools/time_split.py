@@ -9,10 +9,15 @@ word batch holds a word above bpe_doc_max the BPE column carries the refusal ins
 Every split column also carries the fastest and the slowest of its repetitions (`*_ms_min`, `*_ms_max`): the spread a comparison between
 two builds is read against.
 
+`--text mixed` times the rules on a text with what the soup lacks and Split.O200k looks at: made from the soup once on the host, with every
+7th word capitalised, U+0301 behind every 17th letter and "/" and a newline behind every 50th word, cut to `--mib` again.  `--shapes`
+picks the document sizes (0: one document).
+
 Every GPU step — a shape's split and copy columns, then a shape's BPE column — is a child process of its own under `timeout -k 10`.
 The tool stops at the first step that fails: it writes what the steps before it gave, names the failed step and returns its status.
 
-    python tools/time_split.py [--mib 256] [--reps 3] [--rules whitespace,gpt2,cl100k,llama3] [--no-bpe] [--out profiles/r17_split_time.json]
+    python tools/time_split.py [--mib 256] [--reps 3] [--rules whitespace,gpt2,cl100k,llama3,o200k] [--text soup|mixed] [--shapes 0,64,512] [--no-bpe]
+                               [--out profiles/r17_split_time.json]
 """
 import argparse
 import json
@@ -46,7 +51,26 @@ def timed(fn, reps):
     return float(np.median(timed_all(fn, reps)))
 
 
-def step(doc_bytes, mib, reps, bpe_column, rules):
+def mixed_text(soup):
+    """the soup (np.uint8) with capitals, marks, slashes and newlines, cut to the soup's length"""
+    import numpy as np
+    letter = (soup >= 97) & (soup <= 122)
+    first = letter.copy()
+    first[1:] &= ~letter[:-1]                     # a word's first letter
+    last = letter.copy()
+    last[:-1] &= ~letter[1:]                      # ... and its last
+    word_no = np.cumsum(first, dtype=np.int64)    # the word a letter lies in, from 1
+    out = soup.copy()
+    out[first & (word_no % 7 == 0)] -= 32
+    mark = np.flatnonzero(letter & (np.cumsum(letter, dtype=np.int64) % 17 == 0)) + 1
+    trail = np.flatnonzero(last & (word_no % 50 == 0)) + 1
+    pos = np.concatenate((mark, mark, trail, trail))
+    val = np.concatenate((np.full(mark.size, 0xCC, np.uint8), np.full(mark.size, 0x81, np.uint8), np.full(trail.size, 0x2F, np.uint8), np.full(trail.size, 0x0A, np.uint8)))
+    order = np.argsort(pos, kind="stable")
+    return np.insert(out, pos[order], val[order])[:soup.size].copy()
+
+
+def step(doc_bytes, mib, reps, bpe_column, rules, text="soup"):
     """one shape of the batch: the split and copy columns, or the BPE column, as one JSON line on stdout"""
     import torch
     import daachorse_amd as da
@@ -58,6 +82,8 @@ def step(doc_bytes, mib, reps, bpe_column, rules):
     n = int(mib * (1 << 20))
     hay = torch.empty(n, dtype=torch.uint8, device="cuda")
     synth.device_wordsoup(hay, synth.SEEDS["cfg3_dense"], pats, 20)
+    if text == "mixed":
+        hay = torch.from_numpy(mixed_text(hay.cpu().numpy())).cuda()
     if doc_bytes:
         off = torch.arange(0, n + 1, doc_bytes, dtype=torch.int64, device="cuda")
         if int(off[-1]) != n:
@@ -127,17 +153,19 @@ def main():
     ap.add_argument("--bpe", action="store_true", help=argparse.SUPPRESS)       # ... that shape's BPE column
     ap.add_argument("--rules", default="whitespace,gpt2", help="the split columns, by the lower-case names of Split")
     ap.add_argument("--no-bpe", action="store_true", help="leave out the tokenize_bpe_batch column")
+    ap.add_argument("--text", default="soup", choices=("soup", "mixed"), help="mixed: the soup with capitals, marks, slashes and newlines")
+    ap.add_argument("--shapes", default=",".join(map(str, DOC_BYTES)), help="the document sizes, 0 for one document")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rules = [x for x in args.rules.split(",") if x]
     if args.step is not None:
-        step(args.step, args.mib, args.reps, args.bpe, rules)
+        step(args.step, args.mib, args.reps, args.bpe, rules, args.text)
         return
-    res = {"tool": "time_split", "mib": args.mib, "reps": args.reps, "rules": rules}
+    res = {"tool": "time_split", "mib": args.mib, "reps": args.reps, "rules": rules, "text": args.text}
     status = 0
     for bpe_column in (False,) if args.no_bpe else (False, True):
-        for doc_bytes in DOC_BYTES:
-            cmd = [sys.executable, os.path.abspath(__file__), "--step", str(doc_bytes), "--mib", str(args.mib), "--reps", str(args.reps), "--rules", args.rules] + (["--bpe"] if bpe_column else [])
+        for doc_bytes in [int(x) for x in args.shapes.split(",") if x]:
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", str(doc_bytes), "--mib", str(args.mib), "--reps", str(args.reps), "--rules", args.rules, "--text", args.text] + (["--bpe"] if bpe_column else [])
             status, out = run_step(cmd, STEP_SECONDS)
             if status != 0:
                 res["failed_step"] = {"doc_bytes": doc_bytes, "bpe": bpe_column, "status": status}
