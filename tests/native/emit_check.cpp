@@ -96,6 +96,6 @@ int main(int argc, char **argv) {
     // deep = the matches of more than K bytes: one record each in the kernels' list (what find3 / left3 weigh per KiB of text)
     size_t ndeep = 0;
     for (const auto &d : deep) ndeep += d.size();
-    std::printf("OK %lld K=%u C=%u tuples=%zu deep=%zu maxlen=%u\n", n, K, C, got.size(), ndeep, g.max_len);
+    std::printf("OK %lld K=%u C=%u tuples=%zu deep=%zu s16=%d n_deep=%zu maxlen=%u\n", n, K, C, got.size(), ndeep, int(g.s16), g.ehit.size(), g.max_len);
     return 0;
 }

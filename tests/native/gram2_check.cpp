@@ -120,14 +120,14 @@ int main(int argc, char **argv) {
     if (gc_tail != gc_walk) { std::printf("MISMATCH tail records %llu vs %llu\n", (unsigned long long)gc_tail, (unsigned long long)gc_walk); return 1; }
     if (!g.exact_available) {  // count only: the short patterns' share of the checksum is not in the tables that would be staged
         if (gc != rc) { std::printf("MISMATCH count %llu vs %llu\n", (unsigned long long)gc, (unsigned long long)rc); return 1; }
-        std::printf("OK-COUNT %lld K=%u C=%u count=%llu lds=%u\n", n, K, C, (unsigned long long)gc, g.lds_count);
+        std::printf("OK-COUNT %lld K=%u C=%u count=%llu lds=%u s16=%d n_deep=%zu\n", n, K, C, (unsigned long long)gc, g.lds_count, int(g.s16), g.dhit.size());
         return 0;
     }
     if (gc != rc || g1 != r1 || g2 != r2) {
         std::printf("MISMATCH count %llu vs %llu, s1 %08x vs %08x, s2 %08x vs %08x\n", (unsigned long long)gc, (unsigned long long)rc, g1, r1, g2, r2);
         return 1;
     }
-    std::printf("OK %lld K=%u C=%u count=%llu lds=%u/%u ids=%zu deep=%zu s16=%d\n", n, K, C, (unsigned long long)gc, g.lds_count, g.lds_exact,
-                g.hsum.size(), g.dhit.size(), int(g.s16));
+    std::printf("OK %lld K=%u C=%u count=%llu lds=%u/%u ids=%zu deep=%zu s16=%d n_deep=%zu\n", n, K, C, (unsigned long long)gc, g.lds_count, g.lds_exact,
+                g.hsum.size(), g.dhit.size(), int(g.s16), g.dhit.size());
     return 0;
 }

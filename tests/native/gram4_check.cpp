@@ -140,7 +140,7 @@ int main(int argc, char **argv) {
         for (long long pz = 0; pz < n; ++pz) shorts += g.m[ctx_ending_at(pz)] >> 30;
         if (shorts + c_filt != rc) { std::printf("MISMATCH count through the filter %llu want %llu\n", (unsigned long long)(shorts + c_filt), (unsigned long long)rc); return 1; }
     }
-    std::printf("OK K=%u C=%u arith=%d lo=%u count=%llu hits=%llu filter=%d words=%u keys=%u passed=%llu useful=%llu\n", K, C, g.arith ? 1 : 0, g.lo, (unsigned long long)rc,
-                (unsigned long long)hits, have_filter ? 1 : 0, W, g.filter_keys, (unsigned long long)passed, (unsigned long long)useful);
+    std::printf("OK K=%u C=%u arith=%d lo=%u count=%llu hits=%llu filter=%d words=%u keys=%u passed=%llu useful=%llu s16=%d n_deep=%zu\n", K, C, g.arith ? 1 : 0, g.lo, (unsigned long long)rc,
+                (unsigned long long)hits, have_filter ? 1 : 0, W, g.filter_keys, (unsigned long long)passed, (unsigned long long)useful, g.s16 ? 1 : 0, g.dhit_c.size());
     return 0;
 }

@@ -41,7 +41,7 @@ int main(int argc, char **argv) {
     const size_t n = g.dhit_c.size();
     if (!build_gram4_mph(g, s_bytes, seeds)) {
         if (!g.mph_disp.empty() || !g.dhit_h.empty() || g.mph_slots != 0) { std::printf("MISMATCH declined but left tables\n"); return 1; }
-        std::printf("DECLINED K=%u C=%u keys=%zu s_bytes=%u seeds=%u\n", K, C, n, s_bytes, seeds);
+        std::printf("DECLINED K=%u C=%u keys=%zu s_bytes=%u seeds=%u s16=%d n_deep=%zu\n", K, C, n, s_bytes, seeds, g.s16 ? 1 : 0, n);
         return 0;
     }
     if (g.mph_disp.size() > s_bytes || g.mph_disp.size() % 16 != 0 || g.mph_disp.size() != (g.mph.bk8 >> 8)) { std::printf("MISMATCH displacement table %zu bytes, directory %u\n", g.mph_disp.size(), s_bytes); return 1; }
@@ -123,7 +123,7 @@ int main(int argc, char **argv) {
         if (rr.x != rh.x || rr.y != rh.y) { std::printf("MISMATCH record at position %lld\n", pz); return 1; }
     }
     if (ends_r != ends_h || go_r != go_h) { std::printf("MISMATCH ends %llu / %llu go-ons %llu / %llu\n", (unsigned long long)ends_r, (unsigned long long)ends_h, (unsigned long long)go_r, (unsigned long long)go_h); return 1; }
-    std::printf("OK K=%u C=%u keys=%zu buckets=%zu s_bytes=%u slots=%u seed=%u filter=%d hits=%llu passed=%llu ends=%llu goons=%llu\n", K, C, n, g.mph_disp.size(), s_bytes,
-                g.mph_slots, g.mph_seed, have_filter ? 1 : 0, (unsigned long long)hits, (unsigned long long)passed, (unsigned long long)ends_h, (unsigned long long)go_h);
+    std::printf("OK K=%u C=%u keys=%zu buckets=%zu s_bytes=%u slots=%u seed=%u filter=%d hits=%llu passed=%llu ends=%llu goons=%llu s16=%d n_deep=%zu\n", K, C, n, g.mph_disp.size(), s_bytes,
+                g.mph_slots, g.mph_seed, have_filter ? 1 : 0, (unsigned long long)hits, (unsigned long long)passed, (unsigned long long)ends_h, (unsigned long long)go_h, g.s16 ? 1 : 0, n);
     return 0;
 }
