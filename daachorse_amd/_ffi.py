@@ -168,6 +168,10 @@ def lib():
     L.daac_offsets_compose.restype = C.c_int
     L.daac_spans_rebase.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]
     L.daac_spans_rebase.restype = C.c_int
+    L.daac_cut_batch.argtypes = [vp, C.c_int, u8p, vp, sz, C.c_int, vp, P(vp), P(vp), P(vp), P(C.c_uint64), P(C.c_uint64)]
+    L.daac_cut_batch.restype = C.c_int
+    L.daac_tokens_splice.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, P(vp), P(vp), P(vp), P(C.c_uint64)]
+    L.daac_tokens_splice.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

@@ -735,17 +735,30 @@ class DoubleArrayAhoCorasick:
         out.append(DeviceOffsets(offs.value, b.n + 1))
         return self._token_result(out, k.value, device)
 
-    def tokenize_bpe_docs(self, docs, ranks=None, split=Split.Gpt2, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
+    def tokenize_bpe_docs(self, docs, ranks=None, split=Split.Gpt2, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False,
+                          special=None):
         """tokenize_bpe behind a pre-tokenizer split, per document: split_batch cuts the documents into words, tokenize_bpe_batch runs over
         (hay, word_offsets) and daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or
         (ids, spans, offsets) as tokenize_bpe_batch gives them, with document i's tokens in [offsets[i], offsets[i+1]) and spans that
         count from the document's first byte.  `split`: a Split rule (the cached default splitter) or a Splitter.  Host documents are
-        uploaded once; a word above option bpe_doc_max answers 6."""
+        uploaded once; a word above option bpe_doc_max answers 6.  `special`: None, or a SpecialTokens: the batch is cut around the
+        special tokens found in the raw text (SpecialTokens.cut_batch), the chain above runs over the segment batch, so every stretch
+        of text between specials is split as a string of its own, and splice_special puts the result back together per document with
+        each special as the one token of its id.  n_matches stays the tokenizer scan's count."""
         b = _Batch(docs)
         if not b.is_device:
             b = _Batch(_upload(b))
         sp = split if isinstance(split, Splitter) else _default_splitter(split)
         rk = self._ranks(ranks)
+        if special is None:
+            out, k = self._bpe_docs_chain(b, sp, rk, gap, gap_id, spans, engine, stream)
+        else:
+            out, k = _special_docs(b, special, spans, stream, lambda sb: self._bpe_docs_chain(sb, sp, rk, gap, gap_id, spans, engine, stream))
+        return self._token_result(out, k, device)
+
+    def _bpe_docs_chain(self, b, sp, rk, gap, gap_id, spans, engine, stream):
+        """split, tokenize_bpe_batch, spans_rebase and offsets_compose over the device batch b -> ([ids, spans?, doc_offsets] in device
+        memory, n_matches)"""
         wo, dw = sp._run(b, stream)
         ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
         n_words = wo.count - 1
@@ -767,7 +780,7 @@ class DoubleArrayAhoCorasick:
             wo.free()
             dw.free()
         out.append(DeviceOffsets(doc_offs.value, b.n + 1))
-        return self._token_result(out, k.value, device)
+        return out, k.value
 
     # ---- tokenize_wordpiece: BERT's WordPiece (daac_tokenize_wordpiece[_batch]; Standard automata) — greedy longest-match-first over the
     # initial pieces and the "##" continuation pieces of a word of pre-split text; a word with a position no piece covers, or of more
@@ -823,7 +836,7 @@ class DoubleArrayAhoCorasick:
         return self._token_result(out, k.value, device)
 
     def tokenize_wordpiece_docs(self, docs, first_ids, cont_ids, unk_id, max_chars=100, split=Split.Bert, spans=False, engine=Engine.Auto, stream=None,
-                                device=False, normalizer=None):
+                                device=False, normalizer=None, special=None):
         """tokenize_wordpiece behind BERT's pre-tokenizer, per document: split_batch cuts the documents into words, words_space tells
         which of them are whitespace, tokenize_wordpiece_batch runs over (hay, word_offsets) with those words skipped and
         daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or (ids, spans, offsets) as
@@ -832,17 +845,27 @@ class DoubleArrayAhoCorasick:
         Splitter.  Host documents are uploaded once.  `normalizer`: None (the text is taken as it is) or a Normalizer, such as
         bert_normalizer(): the documents are normalized on the device first (with src when spans=True), the chain above runs over the
         normalized batch and spans_to_source makes the spans count from the raw document's first byte, as `tokenizers` reports
-        offsets."""
+        offsets.  `special`: None, or a SpecialTokens ([CLS], [SEP], [MASK] ..): the batch is cut around the special tokens found in
+        the raw text, in front of the normalizer (SpecialTokens.cut_batch), all of the above runs over the segment batch and
+        splice_special puts the result back together per document with each special as the one token of its id.  n_matches stays
+        the tokenizer scan's count."""
         b = _Batch(docs)
         if not b.is_device:
             b = _Batch(_upload(b))
         sp = split if isinstance(split, Splitter) else _default_splitter(split)
         keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
-        if normalizer is None:
-            out, k = self._wordpiece_docs_chain(b, sp, model, spans, engine, stream)
-            return self._token_result(out, k, device)
-        if not isinstance(normalizer, Normalizer):
+        if normalizer is not None and not isinstance(normalizer, Normalizer):
             raise DaachorseError(1, "normalizer is None or a Normalizer")
+        if special is None:
+            out, k = self._wordpiece_docs_norm(b, sp, model, spans, engine, stream, normalizer)
+        else:
+            out, k = _special_docs(b, special, spans, stream, lambda sb: self._wordpiece_docs_norm(sb, sp, model, spans, engine, stream, normalizer))
+        return self._token_result(out, k, device)
+
+    def _wordpiece_docs_norm(self, b, sp, model, spans, engine, stream, normalizer):
+        """_wordpiece_docs_chain over the device batch b, behind the normalizer where there is one -> ([ids, spans?, doc_offsets], n_matches)"""
+        if normalizer is None:
+            return self._wordpiece_docs_chain(b, sp, model, spans, engine, stream)
         norm = normalizer._run(b, stream, spans)   # out, out_offsets[, src]
         try:
             out, k = self._wordpiece_docs_chain(_DeviceBatch(norm[0].ptr, norm[1].ptr, b.n), sp, model, spans, engine, stream)
@@ -856,7 +879,7 @@ class DoubleArrayAhoCorasick:
         finally:
             for o in norm:
                 o.free()
-        return self._token_result(out, k, device)
+        return out, k
 
     def _wordpiece_docs_chain(self, b, sp, model, spans, engine, stream):
         """split, words_space, tokenize_wordpiece_batch, spans_rebase and offsets_compose over the device batch b -> ([ids, spans?,
@@ -920,9 +943,19 @@ class _Replacements:
 
 class _Batch:
     """A batch argument: a sequence of documents (str / bytes / uint8 arrays), packed into one host buffer + n + 1 offsets, or a pair
-    (uint8 CUDA tensor, int64 CUDA tensor of n + 1 offsets) that stays on the device."""
+    (uint8 CUDA tensor, int64 CUDA tensor of n + 1 offsets) that stays on the device; the offsets may also be the DeviceOffsets of
+    split_batch or cut_batch, which are positions in that tensor."""
 
     def __init__(self, docs):
+        if isinstance(docs, tuple) and len(docs) == 2 and hasattr(docs[0], "data_ptr") and isinstance(docs[1], DeviceOffsets):
+            hay, off = docs
+            if not hay.is_cuda or hay.dtype.itemsize != 1 or not hay.is_contiguous() or not off.ptr or off.count < 1:
+                raise DaachorseError(1, "a device batch is (contiguous uint8 CUDA tensor, DeviceOffsets of n + 1 offsets that have not been freed)")
+            if hay.numel() == 0:
+                hay = _one_granule(hay)
+            self.keep = (hay, off)
+            self.hay, self.off, self.n, self.is_device = hay.data_ptr(), off.ptr, off.count - 1, 1
+            return
         if isinstance(docs, tuple) and len(docs) == 2 and hasattr(docs[0], "data_ptr") and hasattr(docs[1], "data_ptr"):
             hay, off = docs
             if not (hay.is_cuda and off.is_cuda):
@@ -1235,6 +1268,106 @@ def offsets_compose(inner, outer, stream=None, device=False):
     out = C.c_void_p()
     _ffi.check(_ffi.lib().daac_offsets_compose(p_in, p_out, n, stream, C.byref(out)))
     return _offsets_result([DeviceOffsets(out.value, n)], device)[0]
+
+
+# ---- special tokens in raw text (daac_cut_batch / daac_tokens_splice): `tokenizers`' added tokens with special=True, tiktoken's
+# allowed_special.  They are found in the raw text, leftmost-longest, in front of the normalizer; each is one token with its own id and
+# every stretch of text between them is tokenized as a string of its own.
+SEGMENT_TEXT = 0xFFFFFFFF   # in seg_values: a text segment
+
+
+class SpecialTokens:
+    """The special tokens of a vocabulary: `tokens` is a {text: id} mapping or a sequence of (text, id), text str or bytes, ids in
+    0 .. 0xFFFFFFFE.  `.pma` is the automaton: a DoubleArrayAhoCorasick with MatchKind.LeftmostLongest and value = id.  (An automaton
+    built elsewhere, a charwise one for instance, is taken as it is: the C call checks it.)"""
+
+    def __init__(self, tokens):
+        if isinstance(tokens, DoubleArrayAhoCorasick):
+            self.pma, self.tokens = tokens, None
+            return
+        items = list(tokens.items()) if hasattr(tokens, "items") else [tuple(t) for t in tokens]
+        seen = {}
+        for text, i in items:
+            t = _as_bytes(text)
+            if not t:
+                raise DaachorseError(1, "a special token is empty")
+            if t in seen:
+                raise DaachorseError(1, f"the special token {text!r} comes twice")
+            if not 0 <= int(i) < SEGMENT_TEXT:
+                raise DaachorseError(1, f"the id of {text!r} is not in 0 .. 0xFFFFFFFE")
+            seen[t] = int(i)
+        self.tokens = seen
+        self.pma = DoubleArrayAhoCorasickBuilder().match_kind(MatchKind.LeftmostLongest).build_with_values(seen.items())
+
+    def _cut(self, b, engine, stream):
+        """-> (seg_offsets, doc_segs, seg_values) of the batch b, in device memory"""
+        so, ds, sv, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_cut_batch(self.pma._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, C.byref(so), C.byref(ds), C.byref(sv),
+                                             C.byref(n), C.byref(k)))
+        values = DeviceMatches(sv.value, n.value, np.dtype(np.uint32))
+        values.n_special = k.value
+        return DeviceOffsets(so.value, n.value + 1), DeviceOffsets(ds.value, b.n + 1), values
+
+    def cut_batch(self, docs, engine=Engine.Auto, stream=None, device=False):
+        """-> (seg_offsets, doc_segs, seg_values): the documents cut at the special tokens.  seg_offsets holds n_segs + 1 positions in
+        the batch's buffer (absolute: (hay, seg_offsets) is a batch itself), document i's segments are [doc_segs[i], doc_segs[i+1]) and
+        seg_values[s] is the special's id or SEGMENT_TEXT; no segment is empty.  np.uint64, np.uint64 and np.uint32 arrays, or
+        DeviceOffsets, DeviceOffsets and DeviceMatches (to_numpy / free) with device=True"""
+        return _offsets_result(self._cut(_Batch(docs), engine, stream), device)
+
+
+def _splice(ids, spans, seg_tok, cut, doc_off, n_docs, stream):
+    """daac_tokens_splice over device addresses -> [ids, spans?, doc_tok] in device memory"""
+    (p_so, n_so), (p_ds, n_ds), (p_sv, n_sv) = _device_ptr(cut[0], 8, "seg_offsets"), _device_ptr(cut[1], 8, "doc_segs"), _device_ptr(cut[2], 4, "seg_values")
+    p_st, n_st = _device_ptr(seg_tok, 8, "seg_tok")
+    n_segs = n_so - 1
+    if n_segs < 0 or n_sv != n_segs or n_st != n_segs + 1 or n_ds != n_docs + 1:
+        raise DaachorseError(1, f"seg_offsets and seg_tok hold n_segs + 1 entries, seg_values n_segs and doc_segs n + 1 = {n_docs + 1}")
+    p_ids = _device_ptr(ids, 4, "ids")[0] if ids is not None else None
+    p_sp = _device_ptr(spans, 8, "spans")[0] if spans is not None else None
+    oi, os_, dt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _ffi.check(_ffi.lib().daac_tokens_splice(p_ids, p_sp, p_st, p_sv, p_so, p_ds, doc_off, n_segs, n_docs, stream, C.byref(oi),
+                                             C.byref(os_) if spans is not None else None, C.byref(dt), C.byref(n)))
+    out = [DeviceMatches(oi.value, n.value, np.dtype(np.uint32))]
+    if spans is not None:
+        out.append(DeviceMatches(os_.value, n.value, SPAN_DTYPE))
+    out.append(DeviceOffsets(dt.value, n_docs + 1))
+    return out
+
+
+def splice_special(ids, spans, seg_tok, cut, docs, stream=None, device=False):
+    """daac_tokens_splice: what a tokenizer made of the segment batch of SpecialTokens.cut_batch(docs, device=True), put back together
+    per document.  `ids` (uint32), `spans` (pairs of 8-byte offsets relative to the segment, or None) and `seg_tok` (n_segs + 1 token
+    offsets per segment) are that tokenizer's results in device memory (DeviceMatches / DeviceOffsets, or contiguous CUDA tensors),
+    `cut` the three results of cut_batch, `docs` the batch it was given.  A text segment's tokens are copied, a special segment is the
+    one token of its id whatever lies under it, and spans count from the document's first byte.  -> (ids, doc_tok) or (ids, spans,
+    doc_tok): np.uint32[T], np.uint64[T, 2], np.uint64[n + 1]; device=True: DeviceMatches, DeviceMatches, DeviceOffsets"""
+    if not (isinstance(cut, (tuple, list)) and len(cut) == 3):
+        raise DaachorseError(1, "cut is (seg_offsets, doc_segs, seg_values) as cut_batch(device=True) gives them")
+    b = _Batch(docs)
+    off, keep = b.off, None
+    if not b.is_device:
+        import torch
+        keep = torch.from_numpy(b.offsets.astype(np.int64)).cuda()
+        off = keep.data_ptr()
+    return _offsets_result(_splice(ids, spans, seg_tok, cut, off, b.n, stream), device)
+
+
+def _special_docs(b, special, spans, stream, chain):
+    """cut the device batch b, run `chain` (segment batch -> ([ids, spans?, seg_tok], n_matches)) and splice -> ([ids, spans?, doc_tok], n_matches)"""
+    if not isinstance(special, SpecialTokens):
+        raise DaachorseError(1, "special is None or a SpecialTokens")
+    cut = special._cut(b, Engine.Auto, stream)
+    try:
+        out, k = chain(_DeviceBatch(b.hay, cut[0].ptr, cut[0].count - 1))
+        try:
+            return _splice(out[0], out[1] if spans else None, out[-1], cut, b.off, b.n, stream), k
+        finally:
+            for o in out:
+                o.free()
+    finally:
+        for o in cut:
+            o.free()
 
 
 class Norm(enum.IntEnum):

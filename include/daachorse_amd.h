@@ -58,7 +58,9 @@ extern "C" {
  *   (6, likewise: daac_tokenize_wordpiece / daac_tokenize_wordpiece_batch — BERT's WordPiece over the same tuple list, on the device —
  *      with the split rule DAAC_SPLIT_BERT and daac_split_words_space in front of it.)
  *   (6, likewise: daac_normalizer_create / daac_normalize_batch / daac_normalize and daac_spans_to_source — a per-code-point rewrite of
- *      a batch, BERT's normalizer among them, on the device.) */
+ *      a batch, BERT's normalizer among them, on the device.)
+ *   (6, likewise: daac_cut_batch / daac_tokens_splice — a batch cut into segments around the special tokens written into its text,
+ *      and a tokenizer's result over the segments put back together per document, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -779,6 +781,60 @@ daac_status daac_tokenize_wordpiece_batch(daac_pma *pma, int engine, const uint8
                                           void *stream, const uint32_t *first_ids, const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id,
                                           uint32_t max_chars, const uint8_t *dev_skip, uint32_t **dev_ids, uint64_t **dev_spans,
                                           uint64_t **dev_tok_offsets, uint64_t *n_tokens, uint64_t *n_matches);
+
+/* ---- special tokens in raw text: cut a batch around them, splice the tokens back ------------------------------------------------------------
+ * What `tokenizers`' AddedVocabulary does with added tokens that are special (`<|endoftext|>`, `[CLS]`, `[MASK]`), and tiktoken with
+ * allowed_special: they are found in the raw text, leftmost-longest, in front of the normalizer; each is one token with its own id, and
+ * every stretch of text between them is normalized, pre-tokenized and tokenized as a string of its own.  `special` is a leftmost
+ * automaton (bytewise or charwise) whose patterns are the special tokens and whose values are their ids; the handle's own leftmost kind
+ * decides among candidates (LeftmostLongest is what `tokenizers` uses).
+ * daac_cut_batch.  For document i = hay[offsets[i], offsets[i+1]) take m_0 .. m_{k-1}, the tuples of leftmost_find_iter on that document
+ *   alone, as daac_scan_batch_device16 with DAAC_LEFTMOST_FIND gives them: ascending, disjoint, none across a document boundary.  The
+ *   document is partitioned into the *special* segments [start(m_j), end(m_j)) with the value value(m_j), and the non-empty stretches
+ *   between them, in front of the first and behind the last: the *text* segments, with the value 0xFFFFFFFF.  There are no empty
+ *   segments: an empty document has none, a document without a match is one text segment, two adjacent specials have nothing between
+ *   them.  *dev_seg_offsets holds *n_segs + 1 u64 positions in hay — absolute, entry 0 is offsets[0], the last entry is offsets[n], so
+ *   (hay, seg_offsets) is a batch that every *_batch call accepts; *dev_doc_segs holds n + 1 u64: document i's segments are
+ *   [doc_segs[i], doc_segs[i+1]); *dev_seg_values holds *n_segs u32 (NULL when there is no segment).  *n_special is the number of
+ *   matches.  All three are device memory, released with daac_device_free.  The call returns after the stream has finished.  n = 0: one
+ *   offset and one doc_segs entry, both 0, and a NULL values pointer.
+ *   Decided before a device is touched, in this order.  Status 1: a NULL special or out-pointer; the batch offset rules of
+ *   daac_scan_count_batch (host offsets; device offsets are validated by the tuple call, with one read-back).  Status 5: a Standard
+ *   automaton.  Status 1: an automaton with "" among its patterns (a record of length 0 among daac_pma_outputs: it cannot be a
+ *   segment), then one with the value 0xFFFFFFFF.  Status 2: a doc_segs above option max_result_bytes (8 bytes a document); the segment
+ *   list likewise (8 bytes a segment), answered before it is allocated.  The tuple list is daac_scan_batch_device16's: its engines and
+ *   their refusals (6) and the max_result_bytes rule of the list are this call's.  A host haystack is copied to the device once.
+ *   daac_last_kernel() says "cut docs=.. matches=.. segs=.." in front of what the tuple call reported.
+ *   Method: one lane per item.  The items are, in document order, every document and behind it its matches: document i's item is
+ *   i + doc_match_offsets[i], its j-th match's one more plus j; an item finds its document by binary search over that, so a document
+ *   that is nothing but ten thousand specials costs what ten thousand documents with one special cost.  A document's item contributes
+ *   1 segment when text stands in front of its first match, or when it has no match and is not empty; a match's item 1 for itself and 1
+ *   more when text follows it.  The counts are summed (one read-back of the total) and a second pass writes each item's segment starts
+ *   and values at its rank; doc_segs[i] is the rank of document i's item.  Integer work only, no atomics: the result is a function of
+ *   the input alone.  Scratch: 8 bytes an item.
+ * daac_tokens_splice.  dev_ids (and dev_spans: {start, end} relative to the segment's first byte; NULL: not wanted) are what some
+ *   tokenizer produced over the segment batch, dev_seg_tok its n_segs + 1 token offsets per segment; dev_seg_values, dev_seg_offsets
+ *   and dev_doc_segs are daac_cut_batch's, dev_doc_offsets (n_docs + 1) the offsets that call was given, all in device memory.  A text
+ *   segment's tokens are copied; a special segment contributes exactly one token, whatever the tokenizer made of its bytes: its id is
+ *   its value and its span is the segment.  Output spans are relative to the document's first byte: a text token's span plus
+ *   seg_offsets[s] - doc_offsets[doc].  *dev_out_ids (*n_tokens u32; NULL when there are none), *dev_out_spans (*n_tokens pairs; a NULL
+ *   dev_out_spans: not wanted, and neither with a NULL dev_spans unless the segment batch has no token) and *dev_doc_tok (n_docs + 1 u64 token offsets per document) are device
+ *   memory, released with daac_device_free.  The call looks at CSR offsets only, so it serves daac_tokenize_batch, _unigram_batch,
+ *   _bpe_batch and _wordpiece_batch alike.  Returns after the stream has finished.
+ *   Status 1: a NULL argument other than dev_spans, dev_out_spans, dev_seg_values with n_segs = 0 and dev_ids when the segment batch has
+ *   no token; n_segs > 0 with n_docs = 0.  Status 2: a result above the process-wide option max_result_bytes (8 bytes a document; 4
+ *   bytes a token, 16 more with spans), answered before it is allocated.  daac_last_kernel() says "splice docs=.. segs=.. tokens=..".
+ *   Method: one lane per segment counts its output tokens (seg_tok[s+1] - seg_tok[s], or 1); the counts are summed (one read-back of
+ *   the total); a wave takes a segment and its lanes the segment's tokens, so a long text segment is not one lane's work; a segment
+ *   finds its document by binary search in doc_segs; doc_tok is the new segment offsets composed with doc_segs (daac_offsets_compose's
+ *   kernel).  Scratch: 8 bytes a segment. */
+daac_status daac_cut_batch(daac_pma *special, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream,
+                           uint64_t **dev_seg_offsets, uint64_t **dev_doc_segs, uint32_t **dev_seg_values,
+                           uint64_t *n_segs, uint64_t *n_special);
+daac_status daac_tokens_splice(const uint32_t *dev_ids, const uint64_t *dev_spans, const uint64_t *dev_seg_tok,
+                               const uint32_t *dev_seg_values, const uint64_t *dev_seg_offsets, const uint64_t *dev_doc_segs,
+                               const uint64_t *dev_doc_offsets, size_t n_segs, size_t n_docs, void *stream,
+                               uint32_t **dev_out_ids, uint64_t **dev_out_spans, uint64_t **dev_doc_tok, uint64_t *n_tokens);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need
