@@ -35,7 +35,7 @@ daac_status batch_engine(const daac_pma *pma, const DeviceTables *t, int mode, i
         return DAAC_ERR_UNSUPPORTED;
     }
     if (t && engine == DAAC_ENGINE_TIERED && !t->tier_ok) {
-        set_error("TIERED engine not available for this automaton (more than 31 distinct pattern bytes, or not standard)");
+        set_error("TIERED engine not available for this automaton (more than 31 distinct pattern bytes, not standard, or dense_depth's rows do not fit lds_budget)");
         return DAAC_ERR_UNSUPPORTED;
     }
     bp.tier = t && !pma->charwise && !bp.chain && (engine == DAAC_ENGINE_TIERED || (engine == DAAC_ENGINE_AUTO && t->tier_ok));

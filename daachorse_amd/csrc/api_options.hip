@@ -18,6 +18,10 @@ found:
     return true;
 }
 
+// the largest lds_budget: what a workgroup can have on gfx950.  build_tier_tables keeps TierTables::lds_bytes() below its budget, so the
+// segment, histogram and batch kernels can all be launched with the tables of any accepted budget.
+constexpr int64_t kTierLdsBudgetMax = 160 * 1024;
+
 // values an option cannot take (status 1, as an unknown name)
 static bool option_value_ok(const char *name, int id, int64_t value) {
     if (id == OPT_hist_lds_bins && value < 0) { set_error(std::string("option ") + name + " counts LDS bins: it cannot be negative"); return false; }
@@ -27,6 +31,20 @@ static bool option_value_ok(const char *name, int id, int64_t value) {
     }
     if (id == OPT_bpe_doc_max && (value < 1 || value > 65536)) {
         set_error(std::string("option ") + name + " is the longest document tokenize_bpe merges, in bytes: 1 .. 65536");
+        return false;
+    }
+    // the TIERED re-pack's three (read at upload): a budget beyond what a workgroup can have would give a large dictionary tables no launch
+    // accepts, a negative one would wrap to that; a rows share above 100 % would let the rows alone pass the budget
+    if (id == OPT_lds_budget && (value < 0 || value > kTierLdsBudgetMax)) {
+        set_error(std::string("option ") + name + " is the LDS the TIERED tables may take per workgroup, in bytes: 0 .. " + std::to_string(kTierLdsBudgetMax));
+        return false;
+    }
+    if (id == OPT_rows_share_pct && (value < 0 || value > 100)) {
+        set_error(std::string("option ") + name + " is a share of lds_budget in per cent: 0 .. 100");
+        return false;
+    }
+    if (id == OPT_dense_depth && (value < -1 || value > INT32_MAX)) {
+        set_error(std::string("option ") + name + " is a depth of the trie (0 = ROOT's row alone), or -1 to have it chosen");
         return false;
     }
     return true;

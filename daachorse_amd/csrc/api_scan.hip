@@ -94,7 +94,7 @@ daac_status make_plan(const daac_pma *pma, const DeviceTables *t, int mode, int 
     }
     heads = mode == DAAC_FIND_OVERLAPPING_NO_SUFFIX;
     if (engine == DAAC_ENGINE_TIERED && !t->tier_ok) {
-        set_error("TIERED engine not available for this automaton (more than 31 distinct pattern bytes, or not standard)");
+        set_error("TIERED engine not available for this automaton (more than 31 distinct pattern bytes, not standard, or dense_depth's rows do not fit lds_budget)");
         return DAAC_ERR_UNSUPPORTED;
     }
     if (engine == DAAC_ENGINE_GRAM) {

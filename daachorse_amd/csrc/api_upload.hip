@@ -777,7 +777,7 @@ daac_status daac_pma_info(const daac_pma *pma, daac_info *info) {
                 f->num_classes = t->tier.C;
                 f->tier_dense_states = t->tier.NA;
                 f->tier_lds_states = t->tier.NB;
-                f->tier_lds_bytes = t->tier.lds_bytes;
+                f->tier_lds_bytes = t->tier.off_cls + 256u;   // (the tables alone: a launch asks for at least 1 KiB, for its reduction scratch)
             }
             f->gram_available = t->gram_ok || t->gram2_ok;
             if (t->gram_ok) {

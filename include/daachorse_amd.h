@@ -168,7 +168,7 @@ typedef struct {
     uint32_t num_classes;     /* byte classes incl. class 0 = "byte occurs in no pattern" */
     uint32_t tier_dense_states;  /* states with a dense, fail-resolved LDS row */
     uint32_t tier_lds_states;    /* + states whose child bitmap lives in LDS */
-    uint32_t tier_lds_bytes;     /* LDS bytes of the automaton tables per workgroup */
+    uint32_t tier_lds_bytes;     /* LDS bytes of the automaton tables per workgroup: at most the lds_budget they were laid out under */
     uint8_t tiered_available;    /* 0 if only the DARRAY engine can run this automaton */
     uint8_t gram_available;      /* the GRAM count engine can run this automaton */
     uint32_t gram_k;             /* context length K of the GRAM tables */
@@ -900,7 +900,15 @@ void daac_stream_close(daac_stream *s);
  * when an automaton is uploaded, the others at every scan.
  *   seg_bytes (0 = auto)        bytes of haystack per lane-segment of the segment scanners
  *   threads (1024), blocks_per_cu (0 = auto)   launch shape of the overlapping scanners
- *   lds_budget (98304), dense_depth (-1 = auto), rows_share_pct (45)   TIERED re-pack
+ *   lds_budget (98304), dense_depth (-1 = auto), rows_share_pct (45)   TIERED re-pack, read at upload:
+ *                               lds_budget     bytes of LDS the tables may take per workgroup, 0 .. 163840 (what a workgroup can have: every
+ *                                              accepted budget gives tables the segment, histogram and batch kernels can be launched with;
+ *                                              one too small for ROOT's row leaves the automaton without the TIERED engine)
+ *                               dense_depth    states up to this depth get a dense, fail-resolved row (0 = ROOT alone); -1 = the deepest level
+ *                                              whose rows fit rows_share_pct of the budget (the whole automaton where all of it fits); a depth
+ *                                              whose rows do not fit the budget leaves the automaton without the TIERED engine
+ *                               rows_share_pct 0 .. 100
+ *                               a value outside these ranges (a negative budget, dense_depth < -1): status 1
  *   gram_lds_budget (161792), gram_region (0 = auto: 16384 for the first table set, 65536 for the second and PFX, 262144 from 2 GiB on; rounded down to a power of two >= 2048), gram_slab (4096), gram_region_small (0 = auto: 32768; gram4: bytes of the small regions the haystack's end is cut into, a power of two <= gram_region), gram_taper_split (-1 = auto; gram4: the byte the small regions begin at, rounded down to a whole region; past the end: none; expert knobs for tests and timing runs: a split in front of the launch's first whole round of large regions makes every wave claim at the start of the scan, and that many adds to one counter at once queue for tens of microseconds), gram_dense (-1 = auto), gram_rank_in_lds (-1 = auto),
  *   gram_ppl (0 = auto: 32 positions per lane and step for automata without short patterns, else 16)
  *   gram_version (0 = auto: `.count()` on the gram4 kernel over the renumbered second table set, count + checksum on the first where it applies;

@@ -453,3 +453,28 @@ def test_options_need_no_device():
     assert _ffi.lib().daac_pma_set_option(None, b"gram_ppl", 16, 0) == 1
     assert _ffi.lib().daac_abi_version() == _ffi.ABI_VERSION == 6
     assert isinstance(da.last_kernel(), str)
+
+
+def test_tier_layout_options_have_ranges():
+    """lds_budget, dense_depth and rows_share_pct (the TIERED re-pack's, read at upload) take the ranges include/daachorse_amd.h gives them:
+    a value outside answers status 1, on a handle and process-wide.  lds_budget ends at the 160 KiB a
+    workgroup can have (a negative one does not wrap into a huge one), rows_share_pct is a percentage, dense_depth a depth or -1."""
+    p, _ = da.DoubleArrayAhoCorasick.deserialize(orc.OraclePma.build(["ab", "b"]).serialize())
+    good = {"lds_budget": (0, 392, 98304, 160 * 1024), "rows_share_pct": (0, 45, 100), "dense_depth": (-1, 0, 3, 1000)}
+    bad = {"lds_budget": (-1, -98304, 160 * 1024 + 1, 1 << 20, (1 << 32) + 98304, -(1 << 63)),
+           "rows_share_pct": (-1, 101, 1000, (1 << 32) + 45), "dense_depth": (-2, -100, 1 << 31, (1 << 32) - 1, -(1 << 63))}
+    defaults = {"lds_budget": 96 * 1024, "dense_depth": -1, "rows_share_pct": 45}
+    try:
+        for name in good:
+            for v in good[name]:
+                p.set_option(name, v)
+                da.set_option(name, v)
+            for v in bad[name]:
+                for setter in (p.set_option, da.set_option):
+                    with pytest.raises(da.DaachorseError) as ei:
+                        setter(name, v)
+                    assert ei.value.code == 1 and name in str(ei.value), (name, v)
+            p.set_option(name)   # the override can always be taken away
+    finally:
+        for name, v in defaults.items():
+            da.set_option(name, v)
