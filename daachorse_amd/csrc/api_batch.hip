@@ -1,9 +1,105 @@
 // C ABI (include/daachorse_amd.h), part 6: batches — many independent documents in one call (daac_scan_count_batch,
 // daac_scan_batch_device16, daac_scan_histogram_batch).  The kernels are batch_kernels.hip and batch_hist_kernels.hip; this file
 // validates, stages host haystacks in windows of whole documents, routes the documents the chain modes cannot give one lane to the
-// single-haystack path, and assembles the results.
+// single-haystack path, and assembles the results.  It also holds the front door the other batch calls share (api_internal.hpp, "api_batch.hip";
+// DESIGN.md, "The batch front door"): the argument rules, the staging of a batch in one piece, the per-document length limit and the
+// single haystack as a batch of one.
 #include "api_internal.hpp"
 #include "batch.hpp"
+
+namespace daac {
+namespace api {
+
+daac_status offsets_decrease(uint64_t doc) {
+    set_error("offsets decrease at document " + std::to_string(doc));
+    return DAAC_ERR_INVALID_ARGUMENT;
+}
+
+daac_status check_batch_args(const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device) {
+    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (n && !hay_is_device) {
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) return offsets_decrease(i);
+        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    return DAAC_OK;
+}
+
+daac_status stage_batch(const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, hipStream_t stream, BatchCheck check, StagedBatch &b) {
+    b.dev_hay = hay;
+    b.d_off = reinterpret_cast<const unsigned long long *>(offsets);
+    if (!hay_is_device) {
+        b.ends[0] = offsets[0];
+        b.ends[1] = offsets[n];
+        const daac_status st = stage_window(hay, b.ends[0], b.ends[1], stream, &b.staged, &b.dev_hay);
+        if (st != DAAC_OK) return st;
+        HIP_TRY(b.off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
+        HIP_TRY(hipMemcpyAsync(b.off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        b.d_off = static_cast<const unsigned long long *>(b.off_buf.p);
+    } else if (check == BatchCheck::kernel) {
+        HIP_TRY(b.off_buf.alloc(3 * sizeof(unsigned long long), stream));
+        unsigned long long *flags = static_cast<unsigned long long *>(b.off_buf.p);
+        HIP_TRY(hipMemsetAsync(flags, 0xff, sizeof(unsigned long long), stream));
+        HIP_TRY(launch_batch_plan(b.d_off, n, 1, nullptr, flags, stream));
+        HIP_TRY(hipMemcpyAsync(flags + 1, b.d_off, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(flags + 2, b.d_off + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        unsigned long long h[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (h[0] != kNoDoc) return offsets_decrease(h[0]);
+        b.ends[0] = h[1];
+        b.ends[1] = h[2];
+    } else if (check == BatchCheck::ends) {
+        HIP_TRY(hipMemcpyAsync(&b.ends[0], b.d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&b.ends[1], b.d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (b.ends[1] < b.ends[0]) { set_error("offsets decrease"); return DAAC_ERR_INVALID_ARGUMENT; }
+    }
+    return DAAC_OK;
+}
+
+daac_status stage_one(const uint8_t *hay, uint64_t len, int hay_is_device, hipStream_t stream, StagedBatch &b) {
+    b.dev_hay = hay;
+    b.ends[0] = 0;
+    b.ends[1] = len;
+    if (!hay_is_device && len) {   // the passes read the text on the device: the whole haystack, once
+        const daac_status st = stage_window(hay, 0, len, stream, &b.staged, &b.dev_hay);
+        if (st != DAAC_OK) return st;
+    }
+    HIP_TRY(b.off_buf.alloc(2 * sizeof(b.ends), stream));   // the two offsets, and 16 bytes for an empty text to be
+    HIP_TRY(hipMemcpyAsync(b.off_buf.p, b.ends, sizeof(b.ends), hipMemcpyHostToDevice, stream));
+    b.d_off = static_cast<const unsigned long long *>(b.off_buf.p);
+    if (!len) b.dev_hay = static_cast<const uint8_t *>(b.off_buf.p) + sizeof(b.ends);
+    return DAAC_OK;
+}
+
+daac_status first_doc_over(uint64_t max_len, const uint64_t *offsets, size_t n, const uint64_t *ends, hipStream_t stream, LongDoc &out) {
+    std::vector<uint64_t> h;
+    if (ends) {
+        if (ends[1] - ends[0] <= max_len) return DAAC_OK;
+        h.resize(n + 1);
+        HIP_TRY(hipMemcpyAsync(h.data(), offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        offsets = h.data();
+        for (size_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) return offsets_decrease(i);
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] - offsets[i] > max_len) { out.doc = i; out.len = offsets[i + 1] - offsets[i]; return DAAC_OK; }
+    return DAAC_OK;
+}
+
+daac_status zero_word(hipStream_t stream, DevPtr &out) {
+    void *z = nullptr;
+    HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
+    out = dev_guard(z, stream);
+    HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
+    return DAAC_OK;
+}
+
+}  // namespace api
+}  // namespace daac
 
 namespace {
 
@@ -57,15 +153,9 @@ daac_status note_d(uint64_t doc) {
 daac_status batch_precheck(const daac_pma *pma, int mode, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device) {
     if (!pma) { set_error("null handle"); return DAAC_ERR_INVALID_ARGUMENT; }
     if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    daac_status st = check_mode_kind(pma, mode);
+    daac_status st = check_mode_kind(pma, mode);   // (5 comes between the two kinds of 1: these three calls' documented order)
     if (st != DAAC_OK) return st;
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    return DAAC_OK;
+    return check_batch_args(hay, offsets, n, hay_is_device);
 }
 
 struct Route { uint64_t pieces = 0, lane_docs = 0, long_docs = 0; };
@@ -87,7 +177,7 @@ daac_status batch_layout(const BatchPlan &bp, const unsigned long long *d_off, u
     unsigned long long *h = pin ? pin : local;
     HIP_TRY(hipMemcpyAsync(h, flags, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    if (h[0] != kNone) { set_error("offsets decrease at document " + std::to_string(h[0])); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (h[0] != kNone) return offsets_decrease(h[0]);
     npieces = h[2];
     return DAAC_OK;
 }
@@ -231,9 +321,9 @@ daac_status tuples_window(daac_pma *pma, DeviceTables *t, const BatchPlan &bp, i
     void *out = nullptr;
     unsigned long long *doffs = nullptr;
     HIP_TRY(dev_malloc(&out, std::max<uint64_t>(tot, 1) * 16, stream));
-    std::unique_ptr<void, std::function<void(void *)>> out_guard(out, [stream](void *p) { dev_free(p, stream); });
+    DevPtr out_guard = dev_guard(out, stream);
     HIP_TRY(dev_malloc(reinterpret_cast<void **>(&doffs), (n + 1) * sizeof(unsigned long long), stream));
-    std::unique_ptr<void, std::function<void(void *)>> off_guard(doffs, [stream](void *p) { dev_free(p, stream); });
+    DevPtr off_guard = dev_guard(doffs, stream);
     a.out = static_cast<uint4 *>(out);
     if (!bp.chain) {
         if (tot) HIP_TRY(launch_batch_pieces(tier, da, chr, a, 2, bp.heads, static_cast<uint32_t>(t->num_cu), bp.threads, stream));
@@ -456,9 +546,9 @@ daac_status hist_window(daac_pma *pma, DeviceTables *t, const BatchPlan &bp, con
     void *out = nullptr;
     unsigned long long *doffs = nullptr;
     HIP_TRY(dev_malloc(&out, std::max<uint64_t>(nrows, 1) * sizeof(daac_slot_count), stream));
-    std::unique_ptr<void, std::function<void(void *)>> out_guard(out, [stream](void *p) { dev_free(p, stream); });
+    DevPtr out_guard = dev_guard(out, stream);
     HIP_TRY(dev_malloc(reinterpret_cast<void **>(&doffs), m * sizeof(unsigned long long), stream));
-    std::unique_ptr<void, std::function<void(void *)>> off_guard(doffs, [stream](void *p) { dev_free(p, stream); });
+    DevPtr off_guard = dev_guard(doffs, stream);
     HIP_TRY(launch_batch_hist_copy(h.rec, roff, h.rowcnt, n, nrows, static_cast<unsigned long long *>(out), stream));
     HIP_TRY(hipMemcpyAsync(doffs, h.rowcnt, m * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));   // (the scratch of this window is freed next)
@@ -535,10 +625,8 @@ daac_status daac_scan_batch_device16(daac_pma *pma, int mode, int engine, const 
     if ((st = batch_engine(pma, nullptr, mode, engine, bp)) != DAAC_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // one offset, 0
-        void *z = nullptr;
-        HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
-        std::unique_ptr<void, std::function<void(void *)>> g_z(z, [stream](void *q) { dev_free(q, stream); });
-        HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
+        DevPtr g_z;
+        if ((st = zero_word(stream, g_z)) != DAAC_OK) return st;
         HIP_TRY(hipStreamSynchronize(stream));
         *dev_doc_offsets = static_cast<uint64_t *>(g_z.release());
         report(bp, Route{});
@@ -584,16 +672,14 @@ daac_status daac_scan_histogram_batch(daac_pma *pma, int mode, int engine, const
     BatchPlan bp;
     if ((st = batch_engine(pma, nullptr, mode, engine, bp)) != DAAC_OK) return st;
     if (n && !hay_is_device) {   // the lengths the counts cannot serve, before a device is touched
-        const uint64_t limit = hist_doc_limit(bp);
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] - offsets[i] > limit) return hist_doc_too_long(bp, i, offsets[i + 1] - offsets[i]);
+        LongDoc over;
+        (void)first_doc_over(hist_doc_limit(bp), offsets, n, nullptr, nullptr, over);
+        if (over) return hist_doc_too_long(bp, over.doc, over.len);
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // one offset, 0
-        void *z = nullptr;
-        HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
-        std::unique_ptr<void, std::function<void(void *)>> g_z(z, [stream](void *q) { dev_free(q, stream); });
-        HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
+        DevPtr g_z;
+        if ((st = zero_word(stream, g_z)) != DAAC_OK) return st;
         HIP_TRY(hipStreamSynchronize(stream));
         *dev_doc_offsets = static_cast<uint64_t *>(g_z.release());
         report_hist(bp, HistRoute{});

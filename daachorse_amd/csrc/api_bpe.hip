@@ -1,8 +1,9 @@
 // C ABI (include/daachorse_amd.h), part 11: the byte-pair-merge token ids of a text or a batch on the device (daac_tokenize_bpe,
 // daac_tokenize_bpe_batch).  The pieces are the tuple CSR of daac_scan_batch_device16(DAAC_FIND_OVERLAPPING): its engines, refusals and
-// max_result_bytes rule are this call's; the kernels are bpe_kernels.hip.  This file validates, refuses a document above option
-// bpe_doc_max, stages a host text once, copies the ranks, runs the merge pass, sums the counts (one read-back), allocates the result and
-// runs the write pass.  A single haystack is a batch of one document.
+// max_result_bytes rule are this call's; the kernels are bpe_kernels.hip.  This file validates its own arguments, refuses a document
+// above option bpe_doc_max, copies the ranks, runs the merge pass, sums the counts (one read-back), allocates the result and runs the
+// write pass.  The batch arguments' rules, the staging of a host text, the length check of device offsets and the single haystack as a
+// batch of one document are the batch front door's (api_internal.hpp, "api_batch.hip").
 #include "api_internal.hpp"
 #include "bpe.hpp"
 
@@ -48,8 +49,7 @@ daac_status merge(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t be
     uint64_t k = 0;
     daac_status st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream, &list, &doc_first, &k);
     if (st != DAAC_OK) return st;
-    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
-    auto g_list = guard(list), g_first = guard(doc_first);
+    auto g_list = dev_guard(list, stream), g_first = dev_guard(doc_first, stream);
 
     daac::BpeArgs a{};
     a.hay = dev_hay + begin;
@@ -75,7 +75,7 @@ daac_status merge(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t be
 
     void *tok_off = nullptr;
     if (o.dev_tok_offsets) HIP_TRY(dev_malloc(&tok_off, m * sizeof(uint64_t), stream));
-    auto g_off = guard(tok_off);
+    auto g_off = dev_guard(tok_off, stream);
     a.tok_offsets = tok_off ? static_cast<unsigned long long *>(tok_off) : own_off;
 
     HIP_TRY(daac::launch_bpe_merge(a, stream));
@@ -91,9 +91,9 @@ daac_status merge(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t be
     }
     void *ids = nullptr, *spans = nullptr;
     if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    auto g_ids = guard(ids);
+    auto g_ids = dev_guard(ids, stream);
     if (total && o.dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    auto g_spans = guard(spans);
+    auto g_spans = dev_guard(spans, stream);
     a.ids = static_cast<uint32_t *>(ids);
     a.spans = static_cast<unsigned long long *>(spans);
     if (total) HIP_TRY(daac::launch_bpe_write(a, stream));
@@ -127,22 +127,10 @@ daac_status daac_tokenize_bpe(daac_pma *pma, int engine, const uint8_t *hay, siz
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    void *staged = nullptr;
-    const uint8_t *text = hay;
-    if (!hay_is_device && len) {   // the passes read the text on the device
-        if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    DevBuf granule, off_buf;   // an empty text still gives the tuple call a buffer to point at
-    if (!len) {
-        HIP_TRY(granule.alloc(16, stream));
-        text = static_cast<const uint8_t *>(granule.p);
-    }
-    const unsigned long long one_doc[2] = {0, len};
-    HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
-    HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+    StagedBatch b;
+    if ((st = stage_one(hay, len, hay_is_device, stream, b)) != DAAC_OK) return st;
     const Outs o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
-    return merge(pma, engine, text, 0, len, static_cast<const unsigned long long *>(off_buf.p), 1, stream, ranks, n_ranks, cap, gap, gap_id, o);
+    return merge(pma, engine, b.dev_hay, 0, len, b.d_off, 1, stream, ranks, n_ranks, cap, gap, gap_id, o);
 }
 
 daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
@@ -151,14 +139,7 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
     PmaScope scope_(pma);
     daac_status st = bpe_precheck(pma, ranks, n_ranks, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
     if (st != DAAC_OK) return st;
-    // the batch calls' own argument rules
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
     if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
     *dev_ids = nullptr;
     if (dev_spans) *dev_spans = nullptr;
@@ -176,44 +157,17 @@ daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *ha
         return DAAC_OK;
     }
     const uint64_t cap = bpe_doc_max();
-    if (!hay_is_device)
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] - offsets[i] > cap) return doc_too_long(i, offsets[i + 1] - offsets[i], cap);
+    LongDoc over;   // host offsets: before a device is looked for
+    if (!hay_is_device) (void)first_doc_over(cap, offsets, n, nullptr, stream, over);
+    if (over) return doc_too_long(over.doc, over.len, cap);
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    // documents [offsets[0], offsets[n]) on the device, with their offsets
-    void *staged = nullptr;
-    const uint8_t *dev_hay = hay;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    DevBuf off_buf;
-    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
-    if (!hay_is_device) {
-        ends[0] = offsets[0];
-        ends[1] = offsets[n];
-        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    if (!hay_is_device) {
-        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    } else {   // the first and last offset size the scratch; a decreasing pair in between is the tuple call's to refuse (before the merge pass)
-        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (ends[1] < ends[0]) { set_error("offsets decrease"); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (ends[1] - ends[0] > cap) {   // only then can a document of non-decreasing offsets be too long: look at them all
-            std::vector<uint64_t> h(n + 1);
-            HIP_TRY(hipMemcpyAsync(h.data(), d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (size_t i = 0; i < n; ++i)
-                if (h[i + 1] < h[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-            for (size_t i = 0; i < n; ++i)
-                if (h[i + 1] - h[i] > cap) return doc_too_long(i, h[i + 1] - h[i], cap);
-        }
-    }
-    if (!hay_is_device) d_off = static_cast<const unsigned long long *>(off_buf.p);
+    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse (before the merge pass)
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
+    if (hay_is_device && (st = first_doc_over(cap, offsets, n, b.ends, stream, over)) != DAAC_OK) return st;
+    if (over) return doc_too_long(over.doc, over.len, cap);
     const Outs o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
-    return merge(pma, engine, dev_hay, ends[0], ends[1] - ends[0], d_off, n, stream, ranks, n_ranks, cap, gap, gap_id, o);
+    return merge(pma, engine, b.dev_hay, b.ends[0], b.ends[1] - b.ends[0], b.d_off, n, stream, ranks, n_ranks, cap, gap, gap_id, o);
 }
 
 }  // extern "C"

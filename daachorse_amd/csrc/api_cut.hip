@@ -2,29 +2,21 @@
 // automaton (daac_cut_batch) and a tokenizer's result over the segment batch put back together per document (daac_tokens_splice).
 // The tuple list comes from the call that already produces it (daac_scan_batch_device16 with DAAC_LEFTMOST_FIND: its engines, refusals
 // and max_result_bytes rule are this call's); the kernels are cut_kernels.hip and, for the token offsets per document,
-// split_kernels.hip's offsets_compose.  This file validates, stages a host batch once, counts (an exclusive sum and one read-back per
-// call), allocates the result and runs the write pass.
+// split_kernels.hip's offsets_compose.  This file validates its own arguments, counts (an exclusive sum and one read-back per call),
+// allocates the result and runs the write pass.  The batch arguments' rules and the staging of a host batch are the batch front door's
+// (api_internal.hpp, "api_batch.hip").
 #include "api_internal.hpp"
 #include "cut.hpp"
 #include "split.hpp"
 
 namespace {
 
-using DevPtr = std::unique_ptr<void, std::function<void(void *)>>;
-DevPtr guard(void *p, hipStream_t stream) { return DevPtr(p, [stream](void *q) { dev_free(q, stream); }); }
-
 // Everything that is decided before a device is touched, in the header's order: statuses 1, 1 (the offsets), 5, 1, 1, 2.
 daac_status cut_precheck(const daac_pma *pma, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, bool outs_ok) {
     if (!pma || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    daac_status st = check_mode_kind(pma, DAAC_LEFTMOST_FIND);
+    daac_status st = check_batch_args(hay, offsets, n, hay_is_device);
     if (st != DAAC_OK) return st;
+    if ((st = check_mode_kind(pma, DAAC_LEFTMOST_FIND)) != DAAC_OK) return st;
     std::vector<uint32_t> recs(3 * daac_pma_outputs(pma, nullptr, 0));
     daac_pma_outputs(pma, recs.data(), recs.size() / 3);
     for (size_t i = 0; i < recs.size(); i += 3)
@@ -35,22 +27,6 @@ daac_status cut_precheck(const daac_pma *pma, const uint8_t *hay, const uint64_t
         set_error("doc_segs of " + std::to_string(n) + " documents exceeds max_result_bytes");
         return DAAC_ERR_AUTOMATON_SCALE;
     }
-    return DAAC_OK;
-}
-
-struct TupleList {   // what the tuple call hands out, released with the call
-    void *list = nullptr;
-    uint64_t *doc_first = nullptr;
-    hipStream_t s = nullptr;
-    ~TupleList() { dev_free(list, s); dev_free(doc_first, s); }
-};
-
-// one u64 in device memory, zero
-daac_status zero_word(hipStream_t stream, DevPtr &out) {
-    void *z = nullptr;
-    HIP_TRY(dev_malloc(&z, sizeof(uint64_t), stream));
-    out = guard(z, stream);
-    HIP_TRY(hipMemsetAsync(z, 0, sizeof(uint64_t), stream));
     return DAAC_OK;
 }
 
@@ -69,12 +45,11 @@ daac_status daac_cut_batch(daac_pma *special, int engine, const uint8_t *hay, co
     *n_segs = 0;
     *n_special = 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    TupleList tl;
-    tl.s = stream;
+    TupleList tl(stream);
     uint64_t k = 0;
     if (n == 0) {   // no document: the tuple call's one offset, 0, is seg_offsets; doc_segs is one more
         if ((st = daac_scan_batch_device16(special, DAAC_LEFTMOST_FIND, engine, hay, offsets, 0, hay_is_device, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
-        DevPtr g_ds(nullptr, [](void *) {});
+        DevPtr g_ds;
         if ((st = zero_word(stream, g_ds)) != DAAC_OK) return st;
         HIP_TRY(hipStreamSynchronize(stream));
         g_last_kernel = "cut docs=0 matches=0 segs=0 " + g_last_kernel;
@@ -85,27 +60,14 @@ daac_status daac_cut_batch(daac_pma *special, int engine, const uint8_t *hay, co
     }
     DeviceTables *t = nullptr;
     if ((st = get_tables(special, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    // documents [offsets[0], offsets[n]) on the device, with their offsets
-    void *staged = nullptr;
-    const uint8_t *dev_hay = hay;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    DevBuf off_buf;
-    if (!hay_is_device) {
-        if ((st = stage_window(hay, offsets[0], offsets[n], stream, &staged, &dev_hay)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    if (!hay_is_device) {
-        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        d_off = static_cast<const unsigned long long *>(off_buf.p);
-    }
-    // (device offsets are validated by the tuple call: non-decreasing from here on)
-    if ((st = daac_scan_batch_device16(special, DAAC_LEFTMOST_FIND, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream_,
+    StagedBatch b;   // no kernel of this call reads the text, so the ends are not needed: device offsets are validated by the tuple call
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::none, b)) != DAAC_OK) return st;
+    if ((st = daac_scan_batch_device16(special, DAAC_LEFTMOST_FIND, engine, b.dev_hay, reinterpret_cast<const uint64_t *>(b.d_off), n, 1, stream_,
                                        reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
     daac::CutArgs a{};
     a.seg = static_cast<const daac::CutTuple *>(tl.list);
     a.doc_first = reinterpret_cast<const unsigned long long *>(tl.doc_first);
-    a.doc_off = d_off;
+    a.doc_off = b.d_off;
     a.n_docs = n;
     a.k = k;
     // the scratch: the items' counts with the closing entry, their sum, the sum's scratch
@@ -126,11 +88,11 @@ daac_status daac_cut_batch(daac_pma *special, int engine, const uint8_t *hay, co
     }
     void *so = nullptr, *ds = nullptr, *sv = nullptr;
     HIP_TRY(dev_malloc(&so, (segs + 1) * sizeof(uint64_t), stream));
-    DevPtr g_so = guard(so, stream);
+    DevPtr g_so = dev_guard(so, stream);
     HIP_TRY(dev_malloc(&ds, (n + 1) * sizeof(uint64_t), stream));
-    DevPtr g_ds = guard(ds, stream);
+    DevPtr g_ds = dev_guard(ds, stream);
     if (segs) HIP_TRY(dev_malloc(&sv, segs * sizeof(uint32_t), stream));
-    DevPtr g_sv = guard(sv, stream);
+    DevPtr g_sv = dev_guard(sv, stream);
     a.seg_offsets = static_cast<unsigned long long *>(so);
     a.doc_segs = static_cast<unsigned long long *>(ds);
     a.seg_values = static_cast<uint32_t *>(sv);
@@ -190,11 +152,11 @@ daac_status daac_tokens_splice(const uint32_t *dev_ids, const uint64_t *dev_span
     if (total > cap / per_token) { set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
     void *ids = nullptr, *spans = nullptr, *doc_tok = nullptr;
     if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    DevPtr g_ids = guard(ids, stream);
+    DevPtr g_ids = dev_guard(ids, stream);
     if (total && want_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    DevPtr g_spans = guard(spans, stream);
+    DevPtr g_spans = dev_guard(spans, stream);
     HIP_TRY(dev_malloc(&doc_tok, (n_docs + 1) * sizeof(uint64_t), stream));
-    DevPtr g_dt = guard(doc_tok, stream);
+    DevPtr g_dt = dev_guard(doc_tok, stream);
     a.out_ids = static_cast<uint32_t *>(ids);
     a.out_spans = static_cast<unsigned long long *>(spans);
     if (total) HIP_TRY(daac::launch_splice_write(a, stream));

@@ -502,6 +502,58 @@ daac_status stage_window(const uint8_t *host_hay, uint64_t copy_from, uint64_t e
 // daac_match {start, end, value} -> {end u64, length u32, value u32}; 16-byte tuples -> daac_match8 {value, (end - base) | length << end_bits}
 hipError_t launch_repack16(const daac_match *in, void *out, unsigned long long n, hipStream_t stream);
 hipError_t launch_repack8(const void *in, void *out, unsigned long long n, unsigned long long base, uint32_t end_bits, hipStream_t stream);
+// api_batch.hip: the front door of every call that takes (hay, offsets, n, hay_is_device) — DESIGN.md, "The batch front door"
+constexpr unsigned long long kNoDoc = ~0ull;
+// Status 1 before a device is touched: offsets is NULL with n > 0; host offsets that decrease (the walk names the document); hay is NULL
+// with bytes to read (host: a non-empty span; device: any n > 0).
+daac_status check_batch_args(const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device);
+daac_status offsets_decrease(uint64_t doc);   // status 1, "offsets decrease at document <doc>"
+// What stage_batch learns of device offsets (host offsets have been walked by check_batch_args and need none of it):
+//   kernel  the first decreasing pair, by launch_batch_plan, read back with the two ends (one 24-byte read-back): for the calls that run
+//           their own kernels over the offsets next
+//   ends    offsets[0] and offsets[n] (two 8-byte read-backs, one sync); status 1 if they decrease, and the pairs in between are left to
+//           daac_scan_batch_device16, which the caller runs next and which validates them anyway
+//   none    nothing: `ends` stays {0, 0}
+enum class BatchCheck { kernel, ends, none };
+// A batch's text and offsets on the device.  A host text's copy is released with the struct (hipFree).
+struct StagedBatch {
+    void *staged = nullptr;                         // a host text's copy
+    DevBuf off_buf;
+    const uint8_t *dev_hay = nullptr;               // what the offsets count from
+    const unsigned long long *d_off = nullptr;      // n + 1
+    uint64_t ends[2] = {0, 0};                      // offsets[0], offsets[n]
+    StagedBatch() = default;
+    StagedBatch(const StagedBatch &) = delete;
+    StagedBatch &operator=(const StagedBatch &) = delete;
+    ~StagedBatch() { if (staged) (void)hipFree(staged); }
+};
+// n >= 1, check_batch_args passed.  A host text's window [offsets[0], offsets[n]) and its offsets go to the device once; a device batch
+// is taken where it lies and its offsets are checked as `check` says.
+daac_status stage_batch(const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, hipStream_t stream, BatchCheck check, StagedBatch &b);
+// A single haystack as a batch of one document: the text on the device (for an empty one 16 bytes of the call's own, so that no kernel
+// is handed NULL), ends = {0, len} and the two offsets on the device.
+daac_status stage_one(const uint8_t *hay, uint64_t len, int hay_is_device, hipStream_t stream, StagedBatch &b);
+// The first document of more than max_len bytes: out.doc (kNoDoc: there is none) and out.len.  `ends` == NULL: host offsets, walked.
+// Otherwise device offsets with ends = {offsets[0], offsets[n]}: only a span above max_len can hold such a document, and only then are
+// they all read back; a decreasing pair among them answers 1 before any length is looked at.
+struct LongDoc {
+    uint64_t doc = kNoDoc, len = 0;
+    explicit operator bool() const { return doc != kNoDoc; }
+};
+daac_status first_doc_over(uint64_t max_len, const uint64_t *offsets, size_t n, const uint64_t *ends, hipStream_t stream, LongDoc &out);
+struct TupleList {   // what daac_scan_device16 / daac_scan_batch_device16 hand out, released with the call
+    void *list = nullptr;
+    uint64_t *doc_first = nullptr;
+    hipStream_t s = nullptr;
+    explicit TupleList(hipStream_t stream) : s(stream) {}
+    TupleList(const TupleList &) = delete;
+    TupleList &operator=(const TupleList &) = delete;
+    ~TupleList() { dev_free(list, s); dev_free(doc_first, s); }
+};
+// a result buffer on its way to the caller: freed on `stream` unless released
+using DevPtr = std::unique_ptr<void, std::function<void(void *)>>;
+inline DevPtr dev_guard(void *p, hipStream_t stream) { return DevPtr(p, [stream](void *q) { dev_free(q, stream); }); }
+daac_status zero_word(hipStream_t stream, DevPtr &out);   // one u64 in device memory, cleared on `stream` (not waited for)
 // api_select.hip
 // The standing part of the emitter's and the selection's gates, which daac_pma_info's plan reports too (the gates add retries and samples).
 constexpr uint32_t kDenseRecPerKib = 26;   // find3 / left3: more deep matches per KiB than this = text of dictionary words

@@ -1,11 +1,11 @@
 // C ABI (include/daachorse_amd.h), part 14: a per-code-point rewrite of a text or a batch on the device (daac_normalizer_create,
 // daac_normalize_batch, daac_normalize) and the way back from spans over the rewritten text to spans over the input (daac_spans_to_source).
-// No automaton is involved: a normalizer is a list of rules over code points and a pool of replacement bytes.  This file validates, builds
-// the two-stage table on the host, uploads it per device on first use, stages a host text once, marks the document starts (the splitter's
+// No automaton is involved: a normalizer is a list of rules over code points and a pool of replacement bytes.  This file validates its
+// own arguments, builds the two-stage table on the host, uploads it per device on first use, marks the document starts (the splitter's
 // pass), runs the count pass, sums the tile counts (one read-back), allocates the result and runs the write pass; the kernels are
-// normalize_kernels.hip.  A single haystack is a batch of one document.
+// normalize_kernels.hip.  The batch arguments' rules, the staging of a host text, the validation of device offsets and the single haystack
+// as a batch of one document are the batch front door's (api_internal.hpp, "api_batch.hip").
 #include "api_internal.hpp"
-#include "batch.hpp"
 #include "normalize.hpp"
 #include "split.hpp"
 
@@ -21,7 +21,6 @@ struct daac_normalizer {
 
 namespace {
 
-constexpr unsigned long long kNoDoc = ~0ull;
 constexpr uint64_t kSrcLimit = 0xFFFFFFFFull;   // with src a document has fewer bytes than this
 
 daac_status table_of(daac_normalizer *nz, daac::NormTable &out) {
@@ -49,61 +48,9 @@ daac_status table_of(daac_normalizer *nz, daac::NormTable &out) {
     return DAAC_OK;
 }
 
-// Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
-daac_status batch_precheck(const void *handle, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, bool outs_ok) {
-    if (!handle || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    return DAAC_OK;
-}
-
 daac_status too_long_for_src(uint64_t len) {
     set_error("a document of " + std::to_string(len) + " bytes: with src a document has fewer than 2^32 - 1");
     return DAAC_ERR_UNSUPPORTED;
-}
-
-// A batch's text and offsets on the device.
-struct StagedBatch {
-    void *staged = nullptr;                         // a host text's copy
-    DevBuf off_buf;
-    const uint8_t *dev_hay = nullptr;               // what the offsets count from
-    const unsigned long long *d_off = nullptr;      // n + 1
-    uint64_t ends[2] = {0, 0};                      // offsets[0], offsets[n]
-    ~StagedBatch() { if (staged) (void)hipFree(staged); }
-};
-
-// n >= 1.  A host text and its offsets go to the device once; device offsets are validated as daac_scan_count_batch validates them.
-daac_status stage_batch(const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, hipStream_t stream, StagedBatch &b) {
-    b.dev_hay = hay;
-    b.d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    if (!hay_is_device) {
-        b.ends[0] = offsets[0];
-        b.ends[1] = offsets[n];
-        const daac_status st = stage_window(hay, b.ends[0], b.ends[1], stream, &b.staged, &b.dev_hay);
-        if (st != DAAC_OK) return st;
-        HIP_TRY(b.off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(b.off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        b.d_off = static_cast<const unsigned long long *>(b.off_buf.p);
-        return DAAC_OK;
-    }
-    HIP_TRY(b.off_buf.alloc(3 * sizeof(unsigned long long), stream));
-    unsigned long long *flags = static_cast<unsigned long long *>(b.off_buf.p);
-    HIP_TRY(hipMemsetAsync(flags, 0xff, sizeof(unsigned long long), stream));
-    HIP_TRY(daac::launch_batch_plan(b.d_off, n, 1, nullptr, flags, stream));
-    HIP_TRY(hipMemcpyAsync(flags + 1, b.d_off, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(flags + 2, b.d_off + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-    unsigned long long h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (h[0] != kNoDoc) { set_error("offsets decrease at document " + std::to_string(h[0])); return DAAC_ERR_INVALID_ARGUMENT; }
-    b.ends[0] = h[1];
-    b.ends[1] = h[2];
-    return DAAC_OK;
 }
 
 std::string kernel_line(const daac_normalizer *nz, uint64_t n, uint64_t total, uint64_t out_len, bool src) {
@@ -114,19 +61,18 @@ std::string kernel_line(const daac_normalizer *nz, uint64_t n, uint64_t total, u
 // `text`: the byte at offsets[0] on the device; `d_off`: the n + 1 offsets on the device (n >= 1, checked); ends = {offsets[0], offsets[n]}.
 daac_status normalize_device(daac_normalizer *nz, const uint8_t *text, const uint64_t ends[2], const unsigned long long *d_off, uint64_t n, hipStream_t stream,
                              bool want_src, uint8_t **dev_out, uint64_t **dev_out_offsets, uint32_t **dev_src, uint64_t *out_len) {
-    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
     const uint64_t total = ends[1] - ends[0];
     const uint64_t max_bytes = static_cast<uint64_t>(OPT(max_result_bytes));
     if (n + 1 > max_bytes / sizeof(uint64_t)) { set_error("out_offsets of " + std::to_string(n) + " documents exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
     void *out_offsets = nullptr;
     HIP_TRY(dev_malloc(&out_offsets, (n + 1) * sizeof(uint64_t), stream));
-    auto g_off = guard(out_offsets);
+    auto g_off = dev_guard(out_offsets, stream);
     if (total == 0) {   // documents, all of them empty: no byte
         void *out = nullptr, *src = nullptr;
         HIP_TRY(dev_malloc(&out, 0, stream));
-        auto g_out = guard(out);
+        auto g_out = dev_guard(out, stream);
         if (want_src) HIP_TRY(dev_malloc(&src, 0, stream));
-        auto g_src = guard(src);
+        auto g_src = dev_guard(src, stream);
         HIP_TRY(hipMemsetAsync(out_offsets, 0, (n + 1) * sizeof(uint64_t), stream));
         HIP_TRY(hipStreamSynchronize(stream));
         g_last_kernel = kernel_line(nz, n, 0, 0, want_src);
@@ -177,9 +123,9 @@ daac_status normalize_device(daac_normalizer *nz, const uint8_t *text, const uin
     }
     void *out = nullptr, *src = nullptr;
     HIP_TRY(dev_malloc(&out, bytes, stream));
-    auto g_out = guard(out);
+    auto g_out = dev_guard(out, stream);
     if (want_src) HIP_TRY(dev_malloc(&src, bytes * sizeof(uint32_t), stream));
-    auto g_src = guard(src);
+    auto g_src = dev_guard(src, stream);
     a.out = static_cast<uint8_t *>(out);
     a.src = static_cast<uint32_t *>(src);
     a.out_offsets = static_cast<unsigned long long *>(out_offsets);
@@ -263,26 +209,25 @@ size_t daac_normalizer_table_bytes(const daac_normalizer *nz) {
 daac_status daac_normalize_batch(daac_normalizer *nz, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_, int want_src,
                                  uint8_t **dev_out, uint64_t **dev_out_offsets, uint32_t **dev_src, uint64_t *out_len) {
     PmaScope scope_(nullptr);   // no handle: the process-wide options
-    daac_status st = batch_precheck(nz, hay, offsets, n, hay_is_device, dev_out && dev_out_offsets && out_len && (dev_src || !want_src));
+    if (!nz || !dev_out || !dev_out_offsets || !out_len || (want_src && !dev_src)) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    daac_status st = check_batch_args(hay, offsets, n, hay_is_device);   // status 1 before a device is touched
     if (st != DAAC_OK) return st;
     *dev_out = nullptr;
     *dev_out_offsets = nullptr;
     if (dev_src) *dev_src = nullptr;
     *out_len = 0;
-    if (want_src && n && !hay_is_device)
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] - offsets[i] >= kSrcLimit) return too_long_for_src(offsets[i + 1] - offsets[i]);
+    LongDoc over;   // (device offsets: normalize_device's longest-document pass)
+    if (want_src && !hay_is_device) (void)first_doc_over(kSrcLimit - 1, offsets, n, nullptr, nullptr, over);
+    if (over) return too_long_for_src(over.len);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // no document: no byte and one offset, 0
-        auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
-        void *out = nullptr, *oo = nullptr, *src = nullptr;
+        void *out = nullptr, *src = nullptr;
         HIP_TRY(dev_malloc(&out, 0, stream));
-        auto g_out = guard(out);
-        HIP_TRY(dev_malloc(&oo, sizeof(uint64_t), stream));
-        auto g_oo = guard(oo);
+        auto g_out = dev_guard(out, stream);
+        DevPtr g_oo;
+        if ((st = zero_word(stream, g_oo)) != DAAC_OK) return st;
         if (want_src) HIP_TRY(dev_malloc(&src, 0, stream));
-        auto g_src = guard(src);
-        HIP_TRY(hipMemsetAsync(oo, 0, sizeof(uint64_t), stream));
+        auto g_src = dev_guard(src, stream);
         HIP_TRY(hipStreamSynchronize(stream));
         g_last_kernel = kernel_line(nz, 0, 0, 0, want_src != 0);
         *dev_out = static_cast<uint8_t *>(g_out.release());
@@ -290,8 +235,8 @@ daac_status daac_normalize_batch(daac_normalizer *nz, const uint8_t *hay, const 
         if (want_src) *dev_src = static_cast<uint32_t *>(g_src.release());
         return DAAC_OK;
     }
-    StagedBatch b;
-    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, b)) != DAAC_OK) return st;
+    StagedBatch b;   // the passes read what the offsets say: device offsets are validated first
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::kernel, b)) != DAAC_OK) return st;
     return normalize_device(nz, b.dev_hay + b.ends[0], b.ends, b.d_off, n, stream, want_src != 0, dev_out, dev_out_offsets, dev_src, out_len);
 }
 
@@ -304,19 +249,12 @@ daac_status daac_normalize(daac_normalizer *nz, const uint8_t *hay, size_t len, 
     *out_len = 0;
     if (want_src && len >= kSrcLimit) return too_long_for_src(len);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const uint64_t one_doc[2] = {0, len};
+    PmaScope scope_(nullptr);
+    StagedBatch b;
+    daac_status st = stage_one(hay, len, hay_is_device, stream, b);
+    if (st != DAAC_OK) return st;
     uint64_t *out_offsets = nullptr;
-    daac_status st;
-    if (!hay_is_device) {   // host offsets with the host text
-        const uint8_t none = 0;
-        st = daac_normalize_batch(nz, hay ? hay : &none, one_doc, 1, 0, stream_, want_src, dev_out, &out_offsets, dev_src, out_len);
-    } else {
-        PmaScope scope_(nullptr);
-        DevBuf off_buf;
-        HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
-        st = normalize_device(nz, hay, one_doc, static_cast<const unsigned long long *>(off_buf.p), 1, stream, want_src != 0, dev_out, &out_offsets, dev_src, out_len);
-    }
+    st = normalize_device(nz, b.dev_hay, b.ends, b.d_off, 1, stream, want_src != 0, dev_out, &out_offsets, dev_src, out_len);
     dev_free(out_offsets, stream);
     return st;
 }
@@ -324,19 +262,14 @@ daac_status daac_normalize(daac_normalizer *nz, const uint8_t *hay, size_t len, 
 daac_status daac_spans_to_source(uint64_t *dev_spans, const uint64_t *dev_tok_offsets, const uint64_t *dev_out_offsets, const uint32_t *dev_src, const uint8_t *hay,
                                  const uint64_t *offsets, size_t n, size_t n_tokens, int hay_is_device, void *stream_) {
     if (n_tokens && (!dev_spans || !dev_tok_offsets || !dev_out_offsets || !dev_src)) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
-    daac_status st = batch_precheck(&kNoDoc, hay, offsets, n, hay_is_device, true);
+    daac_status st = check_batch_args(hay, offsets, n, hay_is_device);
     if (st != DAAC_OK) return st;
     if (n_tokens && !n) { set_error("tokens without a document"); return DAAC_ERR_INVALID_ARGUMENT; }
     if (!n_tokens) return DAAC_OK;
     PmaScope scope_(nullptr);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    StagedBatch b;
-    if (!hay_is_device) {
-        if ((st = stage_batch(hay, offsets, n, 0, stream, b)) != DAAC_OK) return st;
-    } else {   // device offsets are those the normalized batch was made from: validated then
-        b.dev_hay = hay;
-        b.d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    }
+    StagedBatch b;   // (device offsets are those the normalized batch was made from: validated then)
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::none, b)) != DAAC_OK) return st;
     HIP_TRY(daac::launch_spans_to_source(reinterpret_cast<unsigned long long *>(dev_spans), reinterpret_cast<const unsigned long long *>(dev_tok_offsets),
                                          reinterpret_cast<const unsigned long long *>(dev_out_offsets), dev_src, b.dev_hay, b.d_off, n, n_tokens, stream));
     HIP_TRY(hipStreamSynchronize(stream));

@@ -1,7 +1,8 @@
 // C ABI (include/daachorse_amd.h), part 8: replace_all on the device (daac_replace_all, daac_replace_all_batch).
 // The tuple list comes from the calls that already produce it (daac_scan_device16, daac_scan_batch_device16: their engines, refusals,
-// note D and max_result_bytes rule are this call's); the kernels are replace_kernels.hip.  This file validates, stages a host haystack
-// once, sizes the result (two exclusive sums and one read-back), allocates it and runs the splice.
+// note D and max_result_bytes rule are this call's); the kernels are replace_kernels.hip.  This file validates its own arguments,
+// sizes the result (two exclusive sums and one read-back), allocates it and runs the splice.  A batch's argument rules and its staging
+// are the batch front door's (api_internal.hpp, "api_batch.hip"); the single haystack stages its host text here, once.
 #include "api_internal.hpp"
 #include "replace.hpp"
 
@@ -23,13 +24,6 @@ daac_status replace_precheck(const daac_pma *pma, int mode, const uint8_t *repl,
     }
     return check_mode_kind(pma, mode);
 }
-
-struct TupleList {   // what the tuple calls hand out, released with the call
-    void *list = nullptr;
-    uint64_t *doc_first = nullptr;
-    hipStream_t s = nullptr;
-    ~TupleList() { dev_free(list, s); dev_free(doc_first, s); }
-};
 
 // The splice of `text` (device, `len` bytes) with the k tuples of `tl`; a batch (n_docs != 0) also gets its out_offsets.
 daac_status splice(DeviceTables *t, const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k, const unsigned long long *d_doc_off, uint64_t n_docs,
@@ -92,14 +86,14 @@ daac_status splice(DeviceTables *t, const uint8_t *text, uint64_t len, TupleList
         HIP_TRY(dev_malloc(reinterpret_cast<void **>(&out_offsets), (n_docs + 1) * sizeof(unsigned long long), stream));
         HIP_TRY(launch_replace_doc_offsets(a, out_offsets, stream));
     }
-    std::unique_ptr<void, std::function<void(void *)>> off_guard(out_offsets, [stream](void *p) { dev_free(p, stream); });
+    DevPtr off_guard = dev_guard(out_offsets, stream);
     void *out = nullptr;
     DevBuf tiles;
     if (total) {
         a.tiles = (total + kSpliceTile - 1) / kSpliceTile;
         HIP_TRY(dev_malloc(&out, (total + 15) & ~15ull, stream));
     }
-    std::unique_ptr<void, std::function<void(void *)>> out_guard(out, [stream](void *p) { dev_free(p, stream); });
+    DevPtr out_guard = dev_guard(out, stream);
     if (total) {
         HIP_TRY(tiles.alloc((a.tiles + 1) * sizeof(long long), stream));
         a.tile_lo = static_cast<long long *>(tiles.p);
@@ -138,8 +132,7 @@ daac_status daac_replace_all(daac_pma *pma, int mode, int engine, const uint8_t 
         if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
     }
     std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    TupleList tl;
-    tl.s = stream;
+    TupleList tl(stream);
     uint64_t k = 0;
     if ((st = daac_scan_device16(pma, mode, engine, len ? text : nullptr, len, 1, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &k)) != DAAC_OK) return st;
     if ((st = splice(t, text, len, tl, k, nullptr, 0, repl, repl_offsets, n_repl, stream, dev_out, nullptr, out_len)) != DAAC_OK) return st;
@@ -153,21 +146,13 @@ daac_status daac_replace_all_batch(daac_pma *pma, int mode, int engine, const ui
     PmaScope scope_(pma);
     daac_status st = replace_precheck(pma, mode, repl, repl_offsets, n_repl, dev_out && dev_out_offsets && out_len && n_replaced);
     if (st != DAAC_OK) return st;
-    // the batch calls' own argument rules
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
     *dev_out = nullptr;
     *dev_out_offsets = nullptr;
     *out_len = 0;
     *n_replaced = 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    TupleList tl;
-    tl.s = stream;
+    TupleList tl(stream);
     uint64_t k = 0;
     if (n == 0) {   // nothing to replace: the tuple call's one offset, 0, is this call's
         if ((st = daac_scan_batch_device16(pma, mode, engine, hay, offsets, 0, hay_is_device, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
@@ -178,31 +163,11 @@ daac_status daac_replace_all_batch(daac_pma *pma, int mode, int engine, const ui
     }
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;
-    // documents [offsets[0], offsets[n]) on the device, with their offsets
-    void *staged = nullptr;
-    const uint8_t *dev_hay = hay;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    DevBuf off_buf;
-    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
-    if (!hay_is_device) {
-        ends[0] = offsets[0];
-        ends[1] = offsets[n];
-        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    if (!hay_is_device) {
-        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        d_off = static_cast<const unsigned long long *>(off_buf.p);
-    }
-    if ((st = daac_scan_batch_device16(pma, mode, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream_,
+    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
+    if ((st = daac_scan_batch_device16(pma, mode, engine, b.dev_hay, reinterpret_cast<const uint64_t *>(b.d_off), n, 1, stream_,
                                        reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
-    if (hay_is_device) {   // (validated by the tuple call: non-decreasing)
-        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if ((st = splice(t, dev_hay + ends[0], ends[1] - ends[0], tl, k, d_off, n, repl, repl_offsets, n_repl, stream, dev_out, dev_out_offsets, out_len)) != DAAC_OK) return st;
+    if ((st = splice(t, b.dev_hay + b.ends[0], b.ends[1] - b.ends[0], tl, k, b.d_off, n, repl, repl_offsets, n_repl, stream, dev_out, dev_out_offsets, out_len)) != DAAC_OK) return st;
     *n_replaced = k;
     return DAAC_OK;
 }

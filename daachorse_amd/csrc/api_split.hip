@@ -1,11 +1,11 @@
 // C ABI (include/daachorse_amd.h), part 12: the pre-tokenizer split of a text or a batch into words on the device (daac_splitter_create,
 // daac_split_batch, daac_split, daac_split_words_space) and the gather that turns offsets over words into offsets over documents (daac_offsets_compose).  No
-// automaton is involved: a splitter is a rule and a class table.  This file validates, builds the two-stage class table on the host,
-// uploads it per device on first use, stages a host text once, marks the document starts, runs the flag pass (behind the two scan passes
-// where the rule has scans), sums the tile counts (one read-back), allocates the result and runs the write passes; the kernels are split_kernels.hip.  A single haystack is a batch of one
-// document.
+// automaton is involved: a splitter is a rule and a class table.  This file validates its own arguments, builds the two-stage class table
+// on the host, uploads it per device on first use, marks the document starts, runs the flag pass (behind the two scan passes where the
+// rule has scans), sums the tile counts (one read-back), allocates the result and runs the write passes; the kernels are
+// split_kernels.hip.  The batch arguments' rules, the staging of a host text, the validation of device offsets and the single haystack as
+// a batch of one document are the batch front door's (api_internal.hpp, "api_batch.hip").
 #include "api_internal.hpp"
-#include "batch.hpp"
 #include "split.hpp"
 
 struct daac_splitter {
@@ -17,8 +17,6 @@ struct daac_splitter {
 };
 
 namespace {
-
-constexpr unsigned long long kNoDoc = ~0ull;
 
 daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
     int device = 0;
@@ -42,19 +40,6 @@ daac_status table_of(daac_splitter *sp, daac::SplitTable &out) {
 const char *rule_name(int rule) { return rule == DAAC_SPLIT_GPT2 ? "gpt2" : rule == DAAC_SPLIT_CL100K ? "cl100k" : rule == DAAC_SPLIT_LLAMA3 ? "llama3" : rule == DAAC_SPLIT_BERT ? "bert" : rule == DAAC_SPLIT_O200K ? "o200k" : "whitespace"; }
 bool rule_scans(int rule) { return rule == DAAC_SPLIT_CL100K || rule == DAAC_SPLIT_LLAMA3; }
 
-// Status 1 before a device is touched: the pointers and the batch offset rules of daac_scan_count_batch.
-daac_status split_precheck(const daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, bool outs_ok) {
-    if (!sp || !outs_ok) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    return DAAC_OK;
-}
-
 daac_status too_many_words(uint64_t words) {
     set_error("the list of " + std::to_string(words) + " words exceeds max_result_bytes");
     return DAAC_ERR_AUTOMATON_SCALE;
@@ -63,16 +48,15 @@ daac_status too_many_words(uint64_t words) {
 // `text`: the byte at offsets[0] on the device; `d_off`: the n + 1 offsets on the device (n >= 1, checked); ends = {offsets[0], offsets[n]}.
 daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t ends[2], const unsigned long long *d_off, uint64_t n, hipStream_t stream,
                          uint64_t **dev_word_offsets, uint64_t **dev_doc_words, uint64_t *n_words) {
-    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
     const uint64_t total = ends[1] - ends[0];
     if (n + 1 > static_cast<uint64_t>(OPT(max_result_bytes)) / sizeof(uint64_t)) { set_error("doc_words of " + std::to_string(n) + " documents exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
     void *doc_words = nullptr;
     HIP_TRY(dev_malloc(&doc_words, (n + 1) * sizeof(uint64_t), stream));
-    auto g_docs = guard(doc_words);
+    auto g_docs = dev_guard(doc_words, stream);
     if (total == 0) {   // documents, all of them empty: no word
         void *wo = nullptr;
         HIP_TRY(dev_malloc(&wo, sizeof(uint64_t), stream));
-        auto g_wo = guard(wo);
+        auto g_wo = dev_guard(wo, stream);
         HIP_TRY(hipMemsetAsync(doc_words, 0, (n + 1) * sizeof(uint64_t), stream));
         HIP_TRY(hipMemcpyAsync(wo, &ends[0], sizeof(uint64_t), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -123,7 +107,7 @@ daac_status split_device(daac_splitter *sp, const uint8_t *text, const uint64_t 
     if (words + 1 > static_cast<uint64_t>(OPT(max_result_bytes)) / sizeof(uint64_t)) return too_many_words(words);
     void *wo = nullptr;
     HIP_TRY(dev_malloc(&wo, (words + 1) * sizeof(uint64_t), stream));
-    auto g_wo = guard(wo);
+    auto g_wo = dev_guard(wo, stream);
     a.word_offsets = static_cast<unsigned long long *>(wo);
     a.doc_words = static_cast<unsigned long long *>(doc_words);
     HIP_TRY(daac::launch_split_scatter(a, stream));
@@ -198,56 +182,25 @@ void daac_splitter_free(daac_splitter *sp) {
 daac_status daac_split_batch(daac_splitter *sp, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
                              uint64_t **dev_word_offsets, uint64_t **dev_doc_words, uint64_t *n_words) {
     PmaScope scope_(nullptr);   // no handle: the process-wide options
-    daac_status st = split_precheck(sp, hay, offsets, n, hay_is_device, dev_word_offsets && dev_doc_words && n_words);
+    if (!sp || !dev_word_offsets || !dev_doc_words || !n_words) { set_error("null argument"); return DAAC_ERR_INVALID_ARGUMENT; }
+    daac_status st = check_batch_args(hay, offsets, n, hay_is_device);   // status 1 before a device is touched
     if (st != DAAC_OK) return st;
     *dev_word_offsets = nullptr;
     *dev_doc_words = nullptr;
     *n_words = 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) {   // no document: one word offset and one doc_words entry, both 0
-        void *wo = nullptr, *dw = nullptr;
-        HIP_TRY(dev_malloc(&wo, sizeof(uint64_t), stream));
-        std::unique_ptr<void, std::function<void(void *)>> g_wo(wo, [stream](void *q) { dev_free(q, stream); });
-        HIP_TRY(dev_malloc(&dw, sizeof(uint64_t), stream));
-        std::unique_ptr<void, std::function<void(void *)>> g_dw(dw, [stream](void *q) { dev_free(q, stream); });
-        HIP_TRY(hipMemsetAsync(wo, 0, sizeof(uint64_t), stream));
-        HIP_TRY(hipMemsetAsync(dw, 0, sizeof(uint64_t), stream));
+        DevPtr g_wo, g_dw;
+        if ((st = zero_word(stream, g_wo)) != DAAC_OK || (st = zero_word(stream, g_dw)) != DAAC_OK) return st;
         HIP_TRY(hipStreamSynchronize(stream));
         g_last_kernel = std::string("split rule=") + rule_name(sp->rule) + " docs=0 bytes=0 words=0";
         *dev_word_offsets = static_cast<uint64_t *>(g_wo.release());
         *dev_doc_words = static_cast<uint64_t *>(g_dw.release());
         return DAAC_OK;
     }
-    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
-    void *staged = nullptr;
-    const uint8_t *dev_hay = hay;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    DevBuf off_buf;
-    if (!hay_is_device) {   // the text and its offsets go to the device once
-        ends[0] = offsets[0];
-        ends[1] = offsets[n];
-        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    if (!hay_is_device) {
-        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        d_off = static_cast<const unsigned long long *>(off_buf.p);
-    } else {   // daac_scan_count_batch's validation of device offsets: the first decreasing pair, read back with the two ends
-        HIP_TRY(off_buf.alloc(3 * sizeof(unsigned long long), stream));
-        unsigned long long *flags = static_cast<unsigned long long *>(off_buf.p);
-        HIP_TRY(hipMemsetAsync(flags, 0xff, sizeof(unsigned long long), stream));
-        HIP_TRY(daac::launch_batch_plan(d_off, n, 1, nullptr, flags, stream));
-        HIP_TRY(hipMemcpyAsync(flags + 1, d_off, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(flags + 2, d_off + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-        unsigned long long h[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (h[0] != kNoDoc) { set_error("offsets decrease at document " + std::to_string(h[0])); return DAAC_ERR_INVALID_ARGUMENT; }
-        ends[0] = h[1];
-        ends[1] = h[2];
-    }
-    return split_device(sp, dev_hay + ends[0], ends, d_off, n, stream, dev_word_offsets, dev_doc_words, n_words);
+    StagedBatch b;   // the flag pass reads what the offsets say: device offsets are validated first
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::kernel, b)) != DAAC_OK) return st;
+    return split_device(sp, b.dev_hay + b.ends[0], b.ends, b.d_off, n, stream, dev_word_offsets, dev_doc_words, n_words);
 }
 
 daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, uint64_t **dev_word_offsets, uint64_t *n_words) {
@@ -256,20 +209,12 @@ daac_status daac_split(daac_splitter *sp, const uint8_t *hay, size_t len, int ha
     *dev_word_offsets = nullptr;
     *n_words = 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const uint64_t one_doc[2] = {0, len};
-    if (!hay_is_device) {   // host offsets with the host text
-        uint64_t *doc_words = nullptr;
-        const uint8_t none = 0;
-        const daac_status st = daac_split_batch(sp, hay ? hay : &none, one_doc, 1, 0, stream_, dev_word_offsets, &doc_words, n_words);
-        dev_free(doc_words, stream);
-        return st;
-    }
     PmaScope scope_(nullptr);
-    DevBuf off_buf;
-    HIP_TRY(off_buf.alloc(sizeof(one_doc), stream));
-    HIP_TRY(hipMemcpyAsync(off_buf.p, one_doc, sizeof(one_doc), hipMemcpyHostToDevice, stream));
+    StagedBatch b;
+    daac_status st = stage_one(hay, len, hay_is_device, stream, b);
+    if (st != DAAC_OK) return st;
     uint64_t *doc_words = nullptr;
-    const daac_status st = split_device(sp, hay, one_doc, static_cast<const unsigned long long *>(off_buf.p), 1, stream, dev_word_offsets, &doc_words, n_words);
+    st = split_device(sp, b.dev_hay, b.ends, b.d_off, 1, stream, dev_word_offsets, &doc_words, n_words);
     dev_free(doc_words, stream);
     return st;
 }
@@ -298,7 +243,7 @@ daac_status daac_split_words_space(daac_splitter *sp, const uint8_t *hay, const 
     std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
     void *flags = nullptr;
     HIP_TRY(dev_malloc(&flags, n_words, stream));
-    std::unique_ptr<void, std::function<void(void *)>> g(flags, [stream](void *q) { dev_free(q, stream); });
+    DevPtr g = dev_guard(flags, stream);
     HIP_TRY(daac::launch_split_words_space(tab, dev_hay, reinterpret_cast<const unsigned long long *>(dev_word_offsets), n_words, ends[0], ends[1],
                                            static_cast<uint8_t *>(flags), stream, sp->rule == DAAC_SPLIT_O200K));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -312,7 +257,7 @@ daac_status daac_offsets_compose(const uint64_t *dev_inner, const uint64_t *dev_
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     void *out = nullptr;
     HIP_TRY(dev_malloc(&out, n_outer * sizeof(uint64_t), stream));
-    std::unique_ptr<void, std::function<void(void *)>> g(out, [stream](void *q) { dev_free(q, stream); });
+    DevPtr g = dev_guard(out, stream);
     HIP_TRY(daac::launch_offsets_compose(reinterpret_cast<const unsigned long long *>(dev_inner), reinterpret_cast<const unsigned long long *>(dev_outer), n_outer,
                                          static_cast<unsigned long long *>(out), stream));
     HIP_TRY(hipStreamSynchronize(stream));

@@ -1,7 +1,8 @@
 // C ABI (include/daachorse_amd.h), part 9: tokenize on the device (daac_tokenize, daac_tokenize_batch).
 // The tuple list comes from the calls that already produce it (daac_scan_device16, daac_scan_batch_device16: their engines, refusals,
-// note D and max_result_bytes rule are this call's); the kernels are tokenize_kernels.hip.  This file validates, stages a host haystack
-// once, counts the tokens (two exclusive sums and one read-back), allocates the result and runs the write pass.
+// note D and max_result_bytes rule are this call's); the kernels are tokenize_kernels.hip.  This file validates its own arguments,
+// counts the tokens (two exclusive sums and one read-back), allocates the result and runs the write pass.  A batch's argument rules and
+// its staging are the batch front door's (api_internal.hpp, "api_batch.hip"); the single haystack stages its host text here, once.
 #include "api_internal.hpp"
 #include "tokenize.hpp"
 
@@ -18,13 +19,6 @@ daac_status tokenize_precheck(const daac_pma *pma, int mode, int gap, uint32_t g
     }
     return check_mode_kind(pma, mode);
 }
-
-struct TupleList {   // what the tuple calls hand out, released with the call
-    void *list = nullptr;
-    uint64_t *doc_first = nullptr;
-    hipStream_t s = nullptr;
-    ~TupleList() { dev_free(list, s); dev_free(doc_first, s); }
-};
 
 // The tokens of `text` (device, `len` bytes) with the k tuples of `tl`; a batch (d_doc_off != NULL) also gets its tok_offsets.
 daac_status tokens(const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k, const unsigned long long *d_doc_off, uint64_t n_docs, int gap,
@@ -77,14 +71,13 @@ daac_status tokens(const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k,
         set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
         return DAAC_ERR_AUTOMATON_SCALE;
     }
-    auto guard = [stream](void *p) { return std::unique_ptr<void, std::function<void(void *)>>(p, [stream](void *q) { dev_free(q, stream); }); };
     void *ids = nullptr, *spans = nullptr, *tok_off = nullptr;
     if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    auto g_ids = guard(ids);
+    auto g_ids = dev_guard(ids, stream);
     if (total && dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    auto g_spans = guard(spans);
+    auto g_spans = dev_guard(spans, stream);
     if (d_doc_off) HIP_TRY(dev_malloc(&tok_off, (n_docs + 1) * sizeof(uint64_t), stream));
-    auto g_off = guard(tok_off);
+    auto g_off = dev_guard(tok_off, stream);
     a.ids = static_cast<uint32_t *>(ids);
     a.spans = static_cast<unsigned long long *>(spans);
     a.tok_offsets = static_cast<unsigned long long *>(tok_off);
@@ -121,8 +114,7 @@ daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *ha
         if ((st = stage_window(hay, 0, len, stream, &staged, &text)) != DAAC_OK) return st;
     }
     std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    TupleList tl;
-    tl.s = stream;
+    TupleList tl(stream);
     uint64_t k = 0;
     if ((st = daac_scan_device16(pma, mode, engine, len ? text : nullptr, len, 1, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &k)) != DAAC_OK) return st;
     if ((st = tokens(text, len, tl, k, nullptr, 0, gap, gap_id, stream, dev_ids, dev_spans, nullptr, n_tokens)) != DAAC_OK) return st;
@@ -136,22 +128,14 @@ daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8
     PmaScope scope_(pma);
     daac_status st = tokenize_precheck(pma, mode, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
     if (st != DAAC_OK) return st;
-    // the batch calls' own argument rules
-    if (n && !offsets) { set_error("offsets is NULL with n > 0"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if (n && !hay_is_device) {
-        for (size_t i = 0; i < n; ++i)
-            if (offsets[i + 1] < offsets[i]) { set_error("offsets decrease at document " + std::to_string(i)); return DAAC_ERR_INVALID_ARGUMENT; }
-        if (!hay && offsets[n] != offsets[0]) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    }
-    if (n && hay_is_device && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
     *dev_ids = nullptr;
     if (dev_spans) *dev_spans = nullptr;
     *dev_tok_offsets = nullptr;
     *n_tokens = 0;
     *n_matches = 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    TupleList tl;
-    tl.s = stream;
+    TupleList tl(stream);
     uint64_t k = 0;
     if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
         if ((st = daac_scan_batch_device16(pma, mode, engine, hay, offsets, 0, hay_is_device, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
@@ -162,31 +146,11 @@ daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8
     }
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    // documents [offsets[0], offsets[n]) on the device, with their offsets
-    void *staged = nullptr;
-    const uint8_t *dev_hay = hay;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(offsets);
-    DevBuf off_buf;
-    uint64_t ends[2] = {0, 0};   // offsets[0], offsets[n]
-    if (!hay_is_device) {
-        ends[0] = offsets[0];
-        ends[1] = offsets[n];
-        if ((st = stage_window(hay, ends[0], ends[1], stream, &staged, &dev_hay)) != DAAC_OK) return st;
-    }
-    std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
-    if (!hay_is_device) {
-        HIP_TRY(off_buf.alloc((n + 1) * sizeof(uint64_t), stream));
-        HIP_TRY(hipMemcpyAsync(off_buf.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        d_off = static_cast<const unsigned long long *>(off_buf.p);
-    }
-    if ((st = daac_scan_batch_device16(pma, mode, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream_,
+    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
+    if ((st = daac_scan_batch_device16(pma, mode, engine, b.dev_hay, reinterpret_cast<const uint64_t *>(b.d_off), n, 1, stream_,
                                        reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
-    if (hay_is_device) {   // (validated by the tuple call: non-decreasing)
-        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if ((st = tokens(dev_hay + ends[0], ends[1] - ends[0], tl, k, d_off, n, gap, gap_id, stream, dev_ids, dev_spans, dev_tok_offsets, n_tokens)) != DAAC_OK) return st;
+    if ((st = tokens(b.dev_hay + b.ends[0], b.ends[1] - b.ends[0], tl, k, b.d_off, n, gap, gap_id, stream, dev_ids, dev_spans, dev_tok_offsets, n_tokens)) != DAAC_OK) return st;
     *n_matches = k;
     return DAAC_OK;
 }
