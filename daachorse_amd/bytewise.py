@@ -627,27 +627,20 @@ class DoubleArrayAhoCorasick:
         """-> ids (np.uint32[T]), or (ids, spans) with spans=True (np.uint64[T, 2], {start, end} in bytes); device=True: the same as
         DeviceMatches (to_numpy / free), left in device memory"""
         h = _Haystack(haystack)
-        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        o = _TokenOuts(spans)
         _ffi.check(_ffi.lib().daac_tokenize(self._h, self._replace_mode(mode), int(engine), h.ptr, h.len, h.is_device, stream, int(gap), int(gap_id),
-                                            C.byref(ids), C.byref(sp) if spans else None, C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        return self._token_result(out, k.value, device)
+                                            *o.ptrs(), *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_batch(self, docs, gap=Gap.Unk, gap_id=0, spans=False, mode=None, engine=Engine.Auto, stream=None, device=False):
         """-> (ids, offsets) or (ids, spans, offsets): every document is tokenized as a haystack of its own, document i's tokens are
         [offsets[i], offsets[i+1]) (np.uint64[n + 1]) and its spans count from its first byte; device=True: DeviceMatches for ids and
         spans, DeviceOffsets for offsets"""
         b = _Batch(docs)
-        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        o = _TokenOuts(spans, b.n)
         _ffi.check(_ffi.lib().daac_tokenize_batch(self._h, self._replace_mode(mode), int(engine), b.hay, b.off, b.n, b.is_device, stream, int(gap),
-                                                  int(gap_id), C.byref(ids), C.byref(sp) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        out.append(DeviceOffsets(offs.value, b.n + 1))
-        return self._token_result(out, k.value, device)
+                                                  int(gap_id), *o.ptrs(), *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     # ---- tokenize_unigram: the segmentation whose pieces' scores sum highest (daac_tokenize_unigram[_batch]; Standard automata).
     # `scores`: float32, indexed by match value; `unk_score`: the score of an unknown piece, which `gap` makes a byte (Gap.Bytes, id
@@ -664,14 +657,10 @@ class DoubleArrayAhoCorasick:
         score, a np.float32; device=True: ids and spans as DeviceMatches (to_numpy / free), left in device memory"""
         h = _Haystack(haystack)
         sc = self._scores(scores)
-        ids, sp, n, k, score = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
+        o, score = _TokenOuts(spans), C.c_float()
         _ffi.check(_ffi.lib().daac_tokenize_unigram(self._h, int(engine), h.ptr, h.len, h.is_device, stream, sc.ctypes.data if sc.size else None, sc.size,
-                                                    C.c_float(unk_score), int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None, C.byref(n),
-                                                    C.byref(k), C.byref(score)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        res = self._token_result(out, k.value, device)
+                                                    C.c_float(unk_score), int(gap), int(gap_id), *o.ptrs(), *o.counts(), C.byref(score)))
+        res = self._token_result(o.result(), o.k.value, device)
         return (res if spans else (res,)) + (np.float32(score.value),)
 
     def tokenize_unigram_batch(self, docs, scores, unk_score, gap=Gap.Chars, gap_id=0, spans=False, doc_scores=False, engine=Engine.Auto, stream=None,
@@ -680,17 +669,14 @@ class DoubleArrayAhoCorasick:
         document's score.  Document i's tokens are [offsets[i], offsets[i+1]); device=True: DeviceMatches / DeviceOffsets"""
         b = _Batch(docs)
         sc = self._scores(scores)
-        ids, sp, offs, ds, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        o, ds = _TokenOuts(spans, b.n), C.c_void_p()
         _ffi.check(_ffi.lib().daac_tokenize_unigram_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, sc.ctypes.data if sc.size else None,
-                                                          sc.size, C.c_float(unk_score), int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
-                                                          C.byref(offs), C.byref(ds) if doc_scores else None, C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        out.append(DeviceOffsets(offs.value, b.n + 1))
+                                                          sc.size, C.c_float(unk_score), int(gap), int(gap_id), *o.ptrs(),
+                                                          C.byref(ds) if doc_scores else None, *o.counts()))
+        out = o.result()
         if doc_scores:
             out.append(DeviceMatches(ds.value, b.n if ds.value else 0, np.dtype(np.float32)))
-        return self._token_result(out, k.value, device)
+        return self._token_result(out, o.k.value, device)
 
     # ---- tokenize_bpe: byte-pair merging in rank order (daac_tokenize_bpe[_batch]; Standard automata) — tiktoken's byte_pair_merge for
     # one piece of pre-split text.  `ranks`: uint32, indexed by match value (None: a piece's rank is its value; 0xFFFFFFFF: never the
@@ -710,14 +696,10 @@ class DoubleArrayAhoCorasick:
         DeviceMatches (to_numpy / free), left in device memory"""
         h = _Haystack(haystack)
         rk = self._ranks(ranks)
-        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        o = _TokenOuts(spans)
         _ffi.check(_ffi.lib().daac_tokenize_bpe(self._h, int(engine), h.ptr, h.len, h.is_device, stream, None if rk is None else rk.ctypes.data,
-                                                0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
-                                                C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        return self._token_result(out, k.value, device)
+                                                0 if rk is None else rk.size, int(gap), int(gap_id), *o.ptrs(), *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_bpe_batch(self, docs, ranks=None, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False):
         """-> (ids, offsets) or (ids, spans, offsets): every document is merged on its own, document i's tokens are
@@ -725,15 +707,10 @@ class DoubleArrayAhoCorasick:
         spans, DeviceOffsets for offsets"""
         b = _Batch(docs)
         rk = self._ranks(ranks)
-        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        o = _TokenOuts(spans, b.n)
         _ffi.check(_ffi.lib().daac_tokenize_bpe_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, None if rk is None else rk.ctypes.data,
-                                                      0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(sp) if spans else None,
-                                                      C.byref(offs), C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        out.append(DeviceOffsets(offs.value, b.n + 1))
-        return self._token_result(out, k.value, device)
+                                                      0 if rk is None else rk.size, int(gap), int(gap_id), *o.ptrs(), *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_bpe_docs(self, docs, ranks=None, split=Split.Gpt2, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False,
                           special=None):
@@ -759,28 +736,9 @@ class DoubleArrayAhoCorasick:
     def _bpe_docs_chain(self, b, sp, rk, gap, gap_id, spans, engine, stream):
         """split, tokenize_bpe_batch, spans_rebase and offsets_compose over the device batch b -> ([ids, spans?, doc_offsets] in device
         memory, n_matches)"""
-        wo, dw = sp._run(b, stream)
-        ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-        n_words = wo.count - 1
-        try:
-            _ffi.check(_ffi.lib().daac_tokenize_bpe_batch(self._h, int(engine), b.hay, wo.ptr, n_words, 1, stream, None if rk is None else rk.ctypes.data,
-                                                          0 if rk is None else rk.size, int(gap), int(gap_id), C.byref(ids), C.byref(spn) if spans else None,
-                                                          C.byref(offs), C.byref(n), C.byref(k)))
-            out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-            if spans:
-                out.append(DeviceMatches(spn.value, n.value, SPAN_DTYPE))
-            word_tok = DeviceOffsets(offs.value, n_words + 1)
-            try:
-                if spans and n.value:
-                    _ffi.check(_ffi.lib().daac_spans_rebase(spn.value, word_tok.ptr, wo.ptr, dw.ptr, b.off, n_words, b.n, stream))
-                _ffi.check(_ffi.lib().daac_offsets_compose(word_tok.ptr, dw.ptr, b.n + 1, stream, C.byref(doc_offs)))
-            finally:
-                word_tok.free()
-        finally:
-            wo.free()
-            dw.free()
-        out.append(DeviceOffsets(doc_offs.value, b.n + 1))
-        return out, k.value
+        return self._docs_chain(b, sp, spans, stream, False, lambda wo, n_words, flags, o: _ffi.lib().daac_tokenize_bpe_batch(
+            self._h, int(engine), b.hay, wo, n_words, 1, stream, None if rk is None else rk.ctypes.data, 0 if rk is None else rk.size, int(gap), int(gap_id),
+            *o.ptrs(), *o.counts()))
 
     # ---- tokenize_wordpiece: BERT's WordPiece (daac_tokenize_wordpiece[_batch]; Standard automata) — greedy longest-match-first over the
     # initial pieces and the "##" continuation pieces of a word of pre-split text; a word with a position no piece covers, or of more
@@ -809,13 +767,9 @@ class DoubleArrayAhoCorasick:
         DeviceMatches (to_numpy / free), left in device memory"""
         h = _Haystack(word)
         keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
-        ids, sp, n, k = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-        _ffi.check(_ffi.lib().daac_tokenize_wordpiece(self._h, int(engine), h.ptr, h.len, h.is_device, stream, *model, C.byref(ids),
-                                                      C.byref(sp) if spans else None, C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        return self._token_result(out, k.value, device)
+        o = _TokenOuts(spans)
+        _ffi.check(_ffi.lib().daac_tokenize_wordpiece(self._h, int(engine), h.ptr, h.len, h.is_device, stream, *model, *o.ptrs(), *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_wordpiece_batch(self, words, first_ids, cont_ids, unk_id, max_chars=100, skip=None, spans=False, engine=Engine.Auto, stream=None,
                                  device=False):
@@ -826,14 +780,10 @@ class DoubleArrayAhoCorasick:
         b = _Batch(words)
         keep, model = self._wordpiece_model(first_ids, cont_ids, unk_id, max_chars)
         skip_keep, skip_ptr = _skip_flags(skip, b.n)
-        ids, sp, offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-        _ffi.check(_ffi.lib().daac_tokenize_wordpiece_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, *model, skip_ptr, C.byref(ids),
-                                                            C.byref(sp) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
-        out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-        if spans:
-            out.append(DeviceMatches(sp.value, n.value, SPAN_DTYPE))
-        out.append(DeviceOffsets(offs.value, b.n + 1))
-        return self._token_result(out, k.value, device)
+        o = _TokenOuts(spans, b.n)
+        _ffi.check(_ffi.lib().daac_tokenize_wordpiece_batch(self._h, int(engine), b.hay, b.off, b.n, b.is_device, stream, *model, skip_ptr, *o.ptrs(),
+                                                            *o.counts()))
+        return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_wordpiece_docs(self, docs, first_ids, cont_ids, unk_id, max_chars=100, split=Split.Bert, spans=False, engine=Engine.Auto, stream=None,
                                 device=False, normalizer=None, special=None):
@@ -884,25 +834,30 @@ class DoubleArrayAhoCorasick:
     def _wordpiece_docs_chain(self, b, sp, model, spans, engine, stream):
         """split, words_space, tokenize_wordpiece_batch, spans_rebase and offsets_compose over the device batch b -> ([ids, spans?,
         doc_offsets] in device memory, n_matches)"""
+        return self._docs_chain(b, sp, spans, stream, True, lambda wo, n_words, flags, o: _ffi.lib().daac_tokenize_wordpiece_batch(
+            self._h, int(engine), b.hay, wo, n_words, 1, stream, *model, flags, *o.ptrs(), *o.counts()))
+
+    @staticmethod
+    def _docs_chain(b, sp, spans, stream, skip_space, call):
+        """The chain of the two methods above over the device batch b: split, the words_space flags (skip_space), `call(word_offsets,
+        n_words, flags or None, outs)` — the batch call over (hay, word_offsets), which returns its status —, spans_rebase and
+        offsets_compose -> ([ids, spans?, doc_offsets] in device memory, n_matches).  What a step has made is freed if a later one fails."""
         wo, dw = sp._run(b, stream)
-        ids, spn, offs, doc_offs, n, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
         n_words = wo.count - 1
-        flags = None
+        o, doc_offs, flags = _TokenOuts(spans, n_words), C.c_void_p(), None
         try:
-            flags = sp._words_space(b.hay, 1, wo.ptr, n_words, stream)
-            _ffi.check(_ffi.lib().daac_tokenize_wordpiece_batch(self._h, int(engine), b.hay, wo.ptr, n_words, 1, stream, *model, flags.ptr, C.byref(ids),
-                                                                C.byref(spn) if spans else None, C.byref(offs), C.byref(n), C.byref(k)))
-            out = [DeviceMatches(ids.value, n.value, np.dtype(np.uint32))]
-            if spans:
-                out.append(DeviceMatches(spn.value, n.value, SPAN_DTYPE))
-            word_tok = DeviceOffsets(offs.value, n_words + 1)
+            if skip_space:
+                flags = sp._words_space(b.hay, 1, wo.ptr, n_words, stream)
+            _ffi.check(call(wo.ptr, n_words, flags.ptr if skip_space else None, o))
+            out = o.result()
+            word_tok = out.pop()
             try:
-                if spans and n.value:
-                    _ffi.check(_ffi.lib().daac_spans_rebase(spn.value, word_tok.ptr, wo.ptr, dw.ptr, b.off, n_words, b.n, stream))
+                if spans and o.n.value:
+                    _ffi.check(_ffi.lib().daac_spans_rebase(o.sp.value, word_tok.ptr, wo.ptr, dw.ptr, b.off, n_words, b.n, stream))
                 _ffi.check(_ffi.lib().daac_offsets_compose(word_tok.ptr, dw.ptr, b.n + 1, stream, C.byref(doc_offs)))
             except Exception:
-                for o in out:
-                    o.free()
+                for x in out:
+                    x.free()
                 raise
             finally:
                 word_tok.free()
@@ -912,7 +867,7 @@ class DoubleArrayAhoCorasick:
             wo.free()
             dw.free()
         out.append(DeviceOffsets(doc_offs.value, b.n + 1))
-        return out, k.value
+        return out, o.k.value
 
     @staticmethod
     def _token_result(out, n_matches, device):
@@ -925,6 +880,31 @@ class DoubleArrayAhoCorasick:
                 for o in dev:
                     o.free()
         return out[0] if len(out) == 1 else tuple(out)
+
+
+class _TokenOuts:
+    """The out-arguments of a token call (spans optional; n_docs=None: a single haystack, no offsets) and, after the call, its results"""
+
+    def __init__(self, spans, n_docs=None):
+        self.ids, self.n, self.k, self.n_docs = C.c_void_p(), C.c_uint64(), C.c_uint64(), n_docs
+        self.sp = C.c_void_p() if spans else None
+        self.offs = C.c_void_p() if n_docs is not None else None
+
+    def ptrs(self):
+        """dev_ids, dev_spans or NULL and, for a batch, dev_tok_offsets: the call's arguments in this order"""
+        return (C.byref(self.ids), C.byref(self.sp) if self.sp is not None else None) + ((C.byref(self.offs),) if self.offs is not None else ())
+
+    def counts(self):
+        return C.byref(self.n), C.byref(self.k)
+
+    def result(self):
+        """-> [DeviceMatches ids, DeviceMatches spans?, DeviceOffsets offsets?], as _token_result takes them"""
+        out = [DeviceMatches(self.ids.value, self.n.value, np.dtype(np.uint32))]
+        if self.sp is not None:
+            out.append(DeviceMatches(self.sp.value, self.n.value, SPAN_DTYPE))
+        if self.offs is not None:
+            out.append(DeviceOffsets(self.offs.value, self.n_docs + 1))
+        return out
 
 
 class _Replacements:

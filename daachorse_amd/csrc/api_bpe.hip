@@ -1,9 +1,9 @@
 // C ABI (include/daachorse_amd.h), part 11: the byte-pair-merge token ids of a text or a batch on the device (daac_tokenize_bpe,
 // daac_tokenize_bpe_batch).  The pieces are the tuple CSR of daac_scan_batch_device16(DAAC_FIND_OVERLAPPING): its engines, refusals and
-// max_result_bytes rule are this call's; the kernels are bpe_kernels.hip.  This file validates its own arguments, refuses a document
-// above option bpe_doc_max, copies the ranks, runs the merge pass, sums the counts (one read-back), allocates the result and runs the
-// write pass.  The batch arguments' rules, the staging of a host text, the length check of device offsets and the single haystack as a
-// batch of one document are the batch front door's (api_internal.hpp, "api_batch.hip").
+// max_result_bytes rule are this call's; the kernels are bpe_kernels.hip.  This file holds what is the call's own: its precheck, its
+// length limit (option bpe_doc_max) and message, the ranks' upload, the merge pass and the write pass.  The order of an entry's checks,
+// the lattice, the scratch's layout, the sum of the counts and its read-back, the limits, the result's buffers and their hand-over are
+// the token calls' back door's (api_internal.hpp, "api_tokens.hip"), which goes through the batch front door ("api_batch.hip").
 #include "api_internal.hpp"
 #include "bpe.hpp"
 
@@ -33,78 +33,31 @@ daac_status doc_too_long(uint64_t d, uint64_t len, uint64_t cap) {
     return DAAC_ERR_UNSUPPORTED;
 }
 
-struct Outs {   // the caller's out-pointers; the optional ones may be NULL
-    uint32_t **dev_ids;
-    uint64_t **dev_spans;
-    uint64_t **dev_tok_offsets;   // NULL: a single haystack
-    uint64_t *n_tokens, *n_matches;
+struct Model {
+    const uint32_t *ranks;
+    size_t n_ranks;
+    uint64_t cap;   // no document is longer
+    int gap;
+    uint32_t gap_id;
 };
 
-// `dev_hay`: the haystack on the device, document 0 begins at `begin`; `len`: the bytes of all documents; `d_off`: the n + 1 offsets on
-// the device (n >= 1).  No document is longer than `cap`.
-daac_status merge(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t begin, uint64_t len, const unsigned long long *d_off, uint64_t n, hipStream_t stream,
-                  const uint32_t *ranks, size_t n_ranks, uint64_t cap, int gap, uint32_t gap_id, const Outs &o) {
-    daac_match16 *list = nullptr;
-    uint64_t *doc_first = nullptr;
-    uint64_t k = 0;
-    daac_status st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream, &list, &doc_first, &k);
-    if (st != DAAC_OK) return st;
-    auto g_list = dev_guard(list, stream), g_first = dev_guard(doc_first, stream);
-
-    daac::BpeArgs a{};
-    a.hay = dev_hay + begin;
-    a.seg = reinterpret_cast<const daac::BpeTuple *>(list);
-    a.doc_first = reinterpret_cast<const unsigned long long *>(doc_first);
-    a.doc_off = d_off;
-    a.n_docs = n;
-    a.n_ranks = n_ranks;
-    a.doc_max = cap;
-    a.gap = gap;
-    a.gap_id = gap_id;
-    // the slots (24 bytes a position), a single haystack's tok_offsets, the total, the sum's scratch, the ranks
-    const uint64_t pos = len + n, m = n + 1;
-    DevBuf work;
-    HIP_TRY(work.alloc(pos * sizeof(daac::BpeSlot) + (2 + m + exclusive_scan_scratch(m)) * sizeof(unsigned long long) + n_ranks * sizeof(uint32_t), stream));
-    a.slots = static_cast<daac::BpeSlot *>(work.p);
-    unsigned long long *hdr = reinterpret_cast<unsigned long long *>(a.slots + pos);
-    unsigned long long *own_off = hdr + 2;
-    unsigned long long *scan_scratch = own_off + m;
-    uint32_t *d_ranks = reinterpret_cast<uint32_t *>(scan_scratch + exclusive_scan_scratch(m));
-    if (n_ranks) HIP_TRY(hipMemcpyAsync(d_ranks, ranks, n_ranks * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    a.ranks = n_ranks ? d_ranks : nullptr;
-
-    void *tok_off = nullptr;
-    if (o.dev_tok_offsets) HIP_TRY(dev_malloc(&tok_off, m * sizeof(uint64_t), stream));
-    auto g_off = dev_guard(tok_off, stream);
-    a.tok_offsets = tok_off ? static_cast<unsigned long long *>(tok_off) : own_off;
-
-    HIP_TRY(daac::launch_bpe_merge(a, stream));
-    HIP_TRY(daac::launch_exclusive_scan(a.tok_offsets, m, hdr, scan_scratch, stream));
-    unsigned long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, hdr, sizeof(total), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (total > len) { set_error("the token count does not fit the text"); return DAAC_ERR_DEVICE; }   // (never seen: every part has a byte)
-    const uint64_t per_token = sizeof(uint32_t) + (o.dev_spans ? 2 * sizeof(uint64_t) : 0);
-    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
-        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
-        return DAAC_ERR_AUTOMATON_SCALE;
-    }
-    void *ids = nullptr, *spans = nullptr;
-    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    auto g_ids = dev_guard(ids, stream);
-    if (total && o.dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    auto g_spans = dev_guard(spans, stream);
-    a.ids = static_cast<uint32_t *>(ids);
-    a.spans = static_cast<unsigned long long *>(spans);
-    if (total) HIP_TRY(daac::launch_bpe_write(a, stream));
-    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
-    g_last_kernel = "bpe docs=" + std::to_string(n) + " matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
-    *o.dev_ids = static_cast<uint32_t *>(g_ids.release());
-    if (o.dev_spans) *o.dev_spans = static_cast<uint64_t *>(g_spans.release());
-    if (o.dev_tok_offsets) *o.dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
-    *o.n_tokens = total;
-    *o.n_matches = k;
-    return DAAC_OK;
+// the scratch: the slots (24 bytes a position) in front; the ranks behind
+daac_status merge(const LatticeIn &in, const Model &m, const TokenOuts &o) {
+    const uint64_t pos = in.len + in.n;
+    hipStream_t stream = in.stream;
+    return lattice_tokens<daac::BpeArgs>("bpe", in, pos * sizeof(daac::BpeSlot), m.n_ranks * sizeof(uint32_t), o,
+        [&](daac::BpeArgs &a, void *front, void *behind) -> daac_status {
+            a.n_ranks = m.n_ranks;
+            a.doc_max = m.cap;
+            a.gap = m.gap;
+            a.gap_id = m.gap_id;
+            a.slots = static_cast<daac::BpeSlot *>(front);
+            if (m.n_ranks) HIP_TRY(hipMemcpyAsync(behind, m.ranks, m.n_ranks * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            a.ranks = m.n_ranks ? static_cast<const uint32_t *>(behind) : nullptr;
+            HIP_TRY(daac::launch_bpe_merge(a, stream));
+            return DAAC_OK;
+        },
+        [&](const daac::BpeArgs &a) -> daac_status { HIP_TRY(daac::launch_bpe_write(a, stream)); return DAAC_OK; });
 }
 
 }  // namespace
@@ -114,60 +67,21 @@ extern "C" {
 daac_status daac_tokenize_bpe(daac_pma *pma, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, const uint32_t *ranks, size_t n_ranks,
                               int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = bpe_precheck(pma, ranks, n_ranks, gap, gap_id, dev_ids && n_tokens && n_matches);
-    if (st != DAAC_OK) return st;
-    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
-    const uint64_t cap = bpe_doc_max();
-    if (len > cap) return doc_too_long(0, len, cap);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    DeviceTables *t = nullptr;
-    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    StagedBatch b;
-    if ((st = stage_one(hay, len, hay_is_device, stream, b)) != DAAC_OK) return st;
-    const Outs o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
-    return merge(pma, engine, b.dev_hay, 0, len, b.d_off, 1, stream, ranks, n_ranks, cap, gap, gap_id, o);
+    const TokenOuts o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
+    const Model m{ranks, n_ranks, bpe_doc_max(), gap, gap_id};
+    return lattice_entry(pma, bpe_precheck(pma, ranks, n_ranks, gap, gap_id, o.ok(false)), engine, hay, len, hay_is_device, stream_, m.cap,
+                         [&](uint64_t d, uint64_t l) { return doc_too_long(d, l, m.cap); }, o, [&](const LatticeIn &in) { return merge(in, m, o); });
 }
 
 daac_status daac_tokenize_bpe_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
                                     const uint32_t *ranks, size_t n_ranks, int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans,
                                     uint64_t **dev_tok_offsets, uint64_t *n_tokens, uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = bpe_precheck(pma, ranks, n_ranks, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
-    if (st != DAAC_OK) return st;
-    if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
-    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *dev_tok_offsets = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
-        daac_match16 *list = nullptr;
-        uint64_t *doc_first = nullptr;
-        uint64_t k = 0;
-        if ((st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, hay, offsets, 0, hay_is_device, stream_, &list, &doc_first, &k)) != DAAC_OK) return st;
-        *dev_tok_offsets = doc_first;
-        g_last_kernel = "bpe docs=0 matches=0 tokens=0 " + g_last_kernel;
-        return DAAC_OK;
-    }
-    const uint64_t cap = bpe_doc_max();
-    LongDoc over;   // host offsets: before a device is looked for
-    if (!hay_is_device) (void)first_doc_over(cap, offsets, n, nullptr, stream, over);
-    if (over) return doc_too_long(over.doc, over.len, cap);
-    DeviceTables *t = nullptr;
-    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse (before the merge pass)
-    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
-    if (hay_is_device && (st = first_doc_over(cap, offsets, n, b.ends, stream, over)) != DAAC_OK) return st;
-    if (over) return doc_too_long(over.doc, over.len, cap);
-    const Outs o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
-    return merge(pma, engine, b.dev_hay, b.ends[0], b.ends[1] - b.ends[0], b.d_off, n, stream, ranks, n_ranks, cap, gap, gap_id, o);
+    const TokenOuts o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
+    const Model m{ranks, n_ranks, bpe_doc_max(), gap, gap_id};
+    return lattice_entry_batch(pma, bpe_precheck(pma, ranks, n_ranks, gap, gap_id, o.ok(true)), engine, hay, offsets, n, hay_is_device, stream_,
+                               "bpe docs=0 matches=0 tokens=0 ", m.cap, [&](uint64_t d, uint64_t l) { return doc_too_long(d, l, m.cap); }, o,
+                               [&](const LatticeIn &in) { return merge(in, m, o); });
 }
 
 }  // extern "C"

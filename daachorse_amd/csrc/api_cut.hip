@@ -3,8 +3,9 @@
 // The tuple list comes from the call that already produces it (daac_scan_batch_device16 with DAAC_LEFTMOST_FIND: its engines, refusals
 // and max_result_bytes rule are this call's); the kernels are cut_kernels.hip and, for the token offsets per document,
 // split_kernels.hip's offsets_compose.  This file validates its own arguments, counts (an exclusive sum and one read-back per call),
-// allocates the result and runs the write pass.  The batch arguments' rules and the staging of a host batch are the batch front door's
-// (api_internal.hpp, "api_batch.hip").
+// allocates the result and runs the write pass; the splice's read-back, token limit, buffers and hand-over are the token calls' back
+// door's (api_internal.hpp, "api_tokens.hip").  The batch arguments' rules and the staging of a host batch are the batch front door's
+// ("api_batch.hip").
 #include "api_internal.hpp"
 #include "cut.hpp"
 #include "split.hpp"
@@ -111,17 +112,15 @@ daac_status daac_tokens_splice(const uint32_t *dev_ids, const uint64_t *dev_span
                                const uint64_t *dev_seg_offsets, const uint64_t *dev_doc_segs, const uint64_t *dev_doc_offsets, size_t n_segs, size_t n_docs,
                                void *stream_, uint32_t **dev_out_ids, uint64_t **dev_out_spans, uint64_t **dev_doc_tok, uint64_t *n_tokens) {
     PmaScope scope_(nullptr);   // no handle: the process-wide options
-    if (!dev_seg_tok || !dev_seg_offsets || !dev_doc_segs || !dev_doc_offsets || !dev_out_ids || !dev_doc_tok || !n_tokens || (n_segs && !dev_seg_values)) {
+    uint64_t no_matches = 0;   // (the splice has no match count)
+    const TokenOuts o{dev_out_ids, dev_out_spans, dev_doc_tok, n_tokens, &no_matches};
+    if (!dev_seg_tok || !dev_seg_offsets || !dev_doc_segs || !dev_doc_offsets || !o.ok(true) || (n_segs && !dev_seg_values)) {
         set_error("null argument");
         return DAAC_ERR_INVALID_ARGUMENT;
     }
     if (n_segs && !n_docs) { set_error("segments without a document"); return DAAC_ERR_INVALID_ARGUMENT; }
-    *dev_out_ids = nullptr;
-    if (dev_out_spans) *dev_out_spans = nullptr;
-    *dev_doc_tok = nullptr;
-    *n_tokens = 0;
-    const uint64_t cap = static_cast<uint64_t>(OPT(max_result_bytes));
-    if (n_docs + 1 > cap / sizeof(uint64_t)) { set_error("doc_tok of " + std::to_string(n_docs) + " documents exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
+    o.clear();
+    if (n_docs + 1 > static_cast<uint64_t>(OPT(max_result_bytes)) / sizeof(uint64_t)) { set_error("doc_tok of " + std::to_string(n_docs) + " documents exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     daac::SpliceArgs a{};
     a.ids = dev_ids;
@@ -141,32 +140,23 @@ daac_status daac_tokens_splice(const uint32_t *dev_ids, const uint64_t *dev_span
     HIP_TRY(daac::launch_exclusive_scan(a.out_seg_tok, n_segs + 1, hdr, scan_scratch, stream));
     HIP_TRY(hipMemcpyAsync(hdr + 1, a.seg_tok + n_segs, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
     unsigned long long h[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    daac_status st = read_totals(hdr, 2, stream, h);
+    if (st != DAAC_OK) return st;
     const uint64_t total = h[0];
     if (!dev_ids && h[1]) { set_error("dev_ids is NULL with " + std::to_string(h[1]) + " tokens"); return DAAC_ERR_INVALID_ARGUMENT; }
-    // spans: wanted with dev_out_spans, unless the tokens that came in have none (without such tokens the specials' spans are all there is)
+    // spans: wanted with dev_out_spans, unless the tokens that came in have none (without such tokens the specials' spans are all there is);
+    // not wanted, the guard stays empty and the hand-over leaves NULL in dev_out_spans
     const bool want_spans = dev_out_spans && (dev_spans || !h[1]);
     a.spans = reinterpret_cast<const unsigned long long *>(dev_spans);
-    const uint64_t per_token = sizeof(uint32_t) + (want_spans ? 2 * sizeof(uint64_t) : 0);
-    if (total > cap / per_token) { set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes"); return DAAC_ERR_AUTOMATON_SCALE; }
-    void *ids = nullptr, *spans = nullptr, *doc_tok = nullptr;
-    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    DevPtr g_ids = dev_guard(ids, stream);
-    if (total && want_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    DevPtr g_spans = dev_guard(spans, stream);
-    HIP_TRY(dev_malloc(&doc_tok, (n_docs + 1) * sizeof(uint64_t), stream));
-    DevPtr g_dt = dev_guard(doc_tok, stream);
-    a.out_ids = static_cast<uint32_t *>(ids);
-    a.out_spans = static_cast<unsigned long long *>(spans);
+    TokenBufs r;
+    if ((st = token_buffers(total, total, want_spans, true, n_docs, stream, r)) != DAAC_OK) return st;   // (fit = total: the splice has no such bound)
+    a.out_ids = static_cast<uint32_t *>(r.ids.get());
+    a.out_spans = static_cast<unsigned long long *>(r.spans.get());
     if (total) HIP_TRY(daac::launch_splice_write(a, stream));
-    HIP_TRY(daac::launch_offsets_compose(a.out_seg_tok, a.doc_segs, n_docs + 1, static_cast<unsigned long long *>(doc_tok), stream));
+    HIP_TRY(daac::launch_offsets_compose(a.out_seg_tok, a.doc_segs, n_docs + 1, static_cast<unsigned long long *>(r.tok_offsets.get()), stream));
     HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
     g_last_kernel = "splice docs=" + std::to_string(n_docs) + " segs=" + std::to_string(n_segs) + " tokens=" + std::to_string(total);
-    *dev_out_ids = static_cast<uint32_t *>(g_ids.release());
-    if (want_spans) *dev_out_spans = static_cast<uint64_t *>(g_spans.release());
-    *dev_doc_tok = static_cast<uint64_t *>(g_dt.release());
-    *n_tokens = total;
+    hand_over(r, o, total, 0);
     return DAAC_OK;
 }
 

@@ -554,6 +554,128 @@ struct TupleList {   // what daac_scan_device16 / daac_scan_batch_device16 hand 
 using DevPtr = std::unique_ptr<void, std::function<void(void *)>>;
 inline DevPtr dev_guard(void *p, hipStream_t stream) { return DevPtr(p, [stream](void *q) { dev_free(q, stream); }); }
 daac_status zero_word(hipStream_t stream, DevPtr &out);   // one u64 in device memory, cleared on `stream` (not waited for)
+// api_tokens.hip: the back door of every call that returns a token list — DESIGN.md, "The token calls' back door"
+struct TokenOuts {   // the caller's out-pointers
+    uint32_t **dev_ids;
+    uint64_t **dev_spans;         // optional
+    uint64_t **dev_tok_offsets;   // NULL: a single haystack
+    uint64_t *n_tokens, *n_matches;
+    bool ok(bool batch) const { return dev_ids && n_tokens && n_matches && (!batch || dev_tok_offsets); }
+    void clear() const {   // at entry, once the arguments have passed: what a refused call leaves behind
+        *dev_ids = nullptr;
+        if (dev_spans) *dev_spans = nullptr;
+        if (dev_tok_offsets) *dev_tok_offsets = nullptr;
+        *n_tokens = 0;
+        *n_matches = 0;
+    }
+};
+struct TokenBufs { DevPtr ids, spans, tok_offsets; };   // the result on its way to the caller
+// `count` (<= 8) totals at `dev`, read back through pinned_words() (the stack where there are none) and waited for: a call's first sync
+daac_status read_totals(const unsigned long long *dev, unsigned count, hipStream_t stream, unsigned long long *out);
+daac_status alloc_tok_offsets(uint64_t n_docs, hipStream_t stream, TokenBufs &r);   // n_docs + 1 entries
+// The limits and the buffers: status 7 if total > fit, status 2 if the ids (and spans) of `total` tokens exceed max_result_bytes; then ids
+// and spans (both only for total != 0) and, with `offsets`, tok_offsets for n_docs documents.
+daac_status token_buffers(uint64_t total, uint64_t fit, bool want_spans, bool offsets, uint64_t n_docs, hipStream_t stream, TokenBufs &r);
+// After the write pass and the call's closing hipStreamSynchronize: the buffers and the two counts become the caller's.
+void hand_over(TokenBufs &r, const TokenOuts &o, uint64_t total, uint64_t matches);
+// n == 0: the tuple call's one offset, 0, is the token call's; `line` goes in front of its daac_last_kernel string.
+daac_status no_document(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, int hay_is_device, hipStream_t stream, const char *line,
+                        const TokenOuts &o);
+// The lattice tokenizers (bpe, unigram, wordpiece): a batch on the device as their entries hand it to the run step.
+struct LatticeIn {
+    daac_pma *pma;
+    int engine;
+    const uint8_t *dev_hay;           // what the offsets count from; document 0 begins at dev_hay + begin
+    uint64_t begin, len;              // len: the bytes of all documents
+    const unsigned long long *d_off;  // n + 1 offsets on the device, n >= 1
+    uint64_t n;
+    hipStream_t stream;
+};
+daac_status lattice_scan(const LatticeIn &in, TupleList &tl, uint64_t *k);   // the pieces: the overlapping scan's tuple CSR
+// One allocation {front | hdr[2] | own tok_offsets[m] | the sum's scratch | behind}; front_bytes is a multiple of 8.
+struct LatticeScratch {
+    DevBuf buf;
+    void *front = nullptr, *behind = nullptr;
+    unsigned long long *hdr = nullptr, *own_off = nullptr, *scan = nullptr;
+};
+daac_status carve_lattice(size_t front_bytes, size_t behind_bytes, uint64_t m, hipStream_t stream, LatticeScratch &s);
+
+// A lattice tokenizer's run over `in`: the lattice, the scratch, `count(a, front, behind)` — the call fills its own fields of `a`, queues
+// its uploads and launches its count passes, which leave the documents' token counts in a.tok_offsets —, the exclusive sum, the read-back,
+// the limits and the buffers, `write(a)`, the sync, the daac_last_kernel line and the hand-over.
+template <class Args, class Count, class Write>
+daac_status lattice_tokens(const char *name, const LatticeIn &in, size_t front_bytes, size_t behind_bytes, const TokenOuts &o, Count count, Write write) {
+    TupleList tl(in.stream);
+    uint64_t k = 0;
+    daac_status st = lattice_scan(in, tl, &k);
+    if (st != DAAC_OK) return st;
+    const uint64_t m = in.n + 1;
+    LatticeScratch s;
+    if ((st = carve_lattice(front_bytes, behind_bytes, m, in.stream, s)) != DAAC_OK) return st;
+    TokenBufs r;
+    if (o.dev_tok_offsets && (st = alloc_tok_offsets(in.n, in.stream, r)) != DAAC_OK) return st;
+    Args a{};
+    a.hay = in.dev_hay + in.begin;
+    a.seg = static_cast<decltype(a.seg)>(tl.list);
+    a.doc_first = reinterpret_cast<const unsigned long long *>(tl.doc_first);
+    a.doc_off = in.d_off;
+    a.n_docs = in.n;
+    a.tok_offsets = r.tok_offsets ? static_cast<unsigned long long *>(r.tok_offsets.get()) : s.own_off;
+    if ((st = count(a, s.front, s.behind)) != DAAC_OK) return st;
+    HIP_TRY(launch_exclusive_scan(a.tok_offsets, m, s.hdr, s.scan, in.stream));
+    unsigned long long total = 0;
+    if ((st = read_totals(s.hdr, 1, in.stream, &total)) != DAAC_OK) return st;
+    if ((st = token_buffers(total, in.len, o.dev_spans != nullptr, false, 0, in.stream, r)) != DAAC_OK) return st;
+    a.ids = static_cast<uint32_t *>(r.ids.get());
+    a.spans = static_cast<unsigned long long *>(r.spans.get());
+    if (total && (st = write(a)) != DAAC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(in.stream));   // the call's scratch is released next; the result is the caller's from here
+    g_last_kernel = std::string(name) + " docs=" + std::to_string(in.n) + " matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
+    hand_over(r, o, total, k);
+    return DAAC_OK;
+}
+
+// The single-haystack entry of a lattice tokenizer behind its precheck (`pre`): the checks and their order, the outs cleared, a document
+// above max_len refused with too_long(document, bytes), the tables, the haystack staged as a batch of one, run(LatticeIn).
+template <class Outs, class TooLong, class Run>
+daac_status lattice_entry(daac_pma *pma, daac_status pre, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, uint64_t max_len,
+                          TooLong too_long, const Outs &o, Run run) {
+    if (pre != DAAC_OK) return pre;
+    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
+    daac_status st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING);
+    if (st != DAAC_OK) return st;
+    o.clear();
+    if (len > max_len) return too_long(0, len);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    StagedBatch b;
+    if ((st = stage_one(hay, len, hay_is_device, stream, b)) != DAAC_OK) return st;
+    return run(LatticeIn{pma, engine, b.dev_hay, 0, len, b.d_off, 1, stream});
+}
+
+// ... and the batch entry; `line`: "<name> docs=0 matches=0 tokens=0 ", what a batch of no document puts in front of daac_last_kernel.
+template <class Outs, class TooLong, class Run>
+daac_status lattice_entry_batch(daac_pma *pma, daac_status pre, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
+                                const char *line, uint64_t max_len, TooLong too_long, const Outs &o, Run run) {
+    if (pre != DAAC_OK) return pre;
+    daac_status st = check_batch_args(hay, offsets, n, hay_is_device);
+    if (st != DAAC_OK) return st;
+    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
+    o.clear();
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) return no_document(pma, DAAC_FIND_OVERLAPPING, engine, hay, offsets, hay_is_device, stream, line, o);
+    LongDoc over;   // host offsets: before a device is looked for
+    if (!hay_is_device) (void)first_doc_over(max_len, offsets, n, nullptr, stream, over);
+    if (over) return too_long(over.doc, over.len);
+    DeviceTables *t = nullptr;
+    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
+    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse (before the count passes)
+    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
+    if (hay_is_device && (st = first_doc_over(max_len, offsets, n, b.ends, stream, over)) != DAAC_OK) return st;
+    if (over) return too_long(over.doc, over.len);
+    return run(LatticeIn{pma, engine, b.dev_hay, b.ends[0], b.ends[1] - b.ends[0], b.d_off, n, stream});
+}
 // api_select.hip
 // The standing part of the emitter's and the selection's gates, which daac_pma_info's plan reports too (the gates add retries and samples).
 constexpr uint32_t kDenseRecPerKib = 26;   // find3 / left3: more deep matches per KiB than this = text of dictionary words

@@ -1,8 +1,9 @@
 // C ABI (include/daachorse_amd.h), part 9: tokenize on the device (daac_tokenize, daac_tokenize_batch).
 // The tuple list comes from the calls that already produce it (daac_scan_device16, daac_scan_batch_device16: their engines, refusals,
 // note D and max_result_bytes rule are this call's); the kernels are tokenize_kernels.hip.  This file validates its own arguments,
-// counts the tokens (two exclusive sums and one read-back), allocates the result and runs the write pass.  A batch's argument rules and
-// its staging are the batch front door's (api_internal.hpp, "api_batch.hip"); the single haystack stages its host text here, once.
+// counts the tokens (two exclusive sums) and runs the write pass; the read-back of the totals, the max_result_bytes rule, the result's
+// buffers and their hand-over are the token calls' back door's (api_internal.hpp, "api_tokens.hip").  A batch's argument rules and its
+// staging are the batch front door's ("api_batch.hip"); the single haystack stages its host text here, once.
 #include "api_internal.hpp"
 #include "tokenize.hpp"
 
@@ -22,7 +23,7 @@ daac_status tokenize_precheck(const daac_pma *pma, int mode, int gap, uint32_t g
 
 // The tokens of `text` (device, `len` bytes) with the k tuples of `tl`; a batch (d_doc_off != NULL) also gets its tok_offsets.
 daac_status tokens(const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k, const unsigned long long *d_doc_off, uint64_t n_docs, int gap,
-                   uint32_t gap_id, hipStream_t stream, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens) {
+                   uint32_t gap_id, hipStream_t stream, const TokenOuts &o) {
     TokenizeArgs a{};
     a.hay = text;
     a.len = len;
@@ -57,37 +58,22 @@ daac_status tokens(const uint8_t *text, uint64_t len, TupleList &tl, uint64_t k,
     HIP_TRY(launch_exclusive_scan(a.epre, m, hdr + 1, scan_scratch, stream));
     HIP_TRY(launch_tokenize_count(a, stream));
     HIP_TRY(launch_exclusive_scan(a.tile_cnt, tl1, hdr, scan_scratch, stream));
-    unsigned long long *pin = reinterpret_cast<unsigned long long *>(pinned_words());
-    unsigned long long local[2];
-    unsigned long long *h = pin ? pin : local;
-    HIP_TRY(hipMemcpyAsync(h, hdr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned long long h[2];
+    daac_status st = read_totals(hdr, 2, stream, h);
+    if (st != DAAC_OK) return st;
     const uint64_t flagged = h[0];
     a.n_empty = h[1];
     if (flagged > len || a.n_empty > k) { set_error("the token count does not fit the text and its matches"); return DAAC_ERR_DEVICE; }   // (never seen)
     const uint64_t total = flagged + a.n_empty;
-    const uint64_t per_token = sizeof(uint32_t) + (dev_spans ? 2 * sizeof(uint64_t) : 0);
-    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
-        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
-        return DAAC_ERR_AUTOMATON_SCALE;
-    }
-    void *ids = nullptr, *spans = nullptr, *tok_off = nullptr;
-    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    auto g_ids = dev_guard(ids, stream);
-    if (total && dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    auto g_spans = dev_guard(spans, stream);
-    if (d_doc_off) HIP_TRY(dev_malloc(&tok_off, (n_docs + 1) * sizeof(uint64_t), stream));
-    auto g_off = dev_guard(tok_off, stream);
-    a.ids = static_cast<uint32_t *>(ids);
-    a.spans = static_cast<unsigned long long *>(spans);
-    a.tok_offsets = static_cast<unsigned long long *>(tok_off);
-    if (total || tok_off) HIP_TRY(launch_tokenize_write(a, total, stream));
+    TokenBufs r;
+    if ((st = token_buffers(total, total, o.dev_spans != nullptr, d_doc_off != nullptr, n_docs, stream, r)) != DAAC_OK) return st;   // (fit = total: the check above is this call's)
+    a.ids = static_cast<uint32_t *>(r.ids.get());
+    a.spans = static_cast<unsigned long long *>(r.spans.get());
+    a.tok_offsets = static_cast<unsigned long long *>(r.tok_offsets.get());
+    if (total || a.tok_offsets) HIP_TRY(launch_tokenize_write(a, total, stream));
     HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
     g_last_kernel = "tokenize matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
-    *dev_ids = static_cast<uint32_t *>(g_ids.release());
-    if (dev_spans) *dev_spans = static_cast<uint64_t *>(g_spans.release());
-    if (dev_tok_offsets) *dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
-    *n_tokens = total;
+    hand_over(r, o, total, k);
     return DAAC_OK;
 }
 
@@ -98,13 +84,11 @@ extern "C" {
 daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *hay, size_t len, int hay_is_device, void *stream_, int gap, uint32_t gap_id,
                           uint32_t **dev_ids, uint64_t **dev_spans, uint64_t *n_tokens, uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, dev_ids && n_tokens && n_matches);
+    const TokenOuts o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
+    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, o.ok(false));
     if (st != DAAC_OK) return st;
     if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
+    o.clear();
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
@@ -117,42 +101,29 @@ daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *ha
     TupleList tl(stream);
     uint64_t k = 0;
     if ((st = daac_scan_device16(pma, mode, engine, len ? text : nullptr, len, 1, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &k)) != DAAC_OK) return st;
-    if ((st = tokens(text, len, tl, k, nullptr, 0, gap, gap_id, stream, dev_ids, dev_spans, nullptr, n_tokens)) != DAAC_OK) return st;
-    *n_matches = k;
-    return DAAC_OK;
+    return tokens(text, len, tl, k, nullptr, 0, gap, gap_id, stream, o);
 }
 
 daac_status daac_tokenize_batch(daac_pma *pma, int mode, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
                                 int gap, uint32_t gap_id, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens,
                                 uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, dev_ids && dev_tok_offsets && n_tokens && n_matches);
+    const TokenOuts o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
+    daac_status st = tokenize_precheck(pma, mode, gap, gap_id, o.ok(true));
     if (st != DAAC_OK) return st;
     if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *dev_tok_offsets = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
+    o.clear();
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0) return no_document(pma, mode, engine, hay, offsets, hay_is_device, stream, "tokenize matches=0 tokens=0 ", o);
     TupleList tl(stream);
     uint64_t k = 0;
-    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
-        if ((st = daac_scan_batch_device16(pma, mode, engine, hay, offsets, 0, hay_is_device, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
-        *dev_tok_offsets = tl.doc_first;
-        tl.doc_first = nullptr;
-        g_last_kernel = "tokenize matches=0 tokens=0 " + g_last_kernel;
-        return DAAC_OK;
-    }
     DeviceTables *t = nullptr;
     if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
     StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse
     if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
     if ((st = daac_scan_batch_device16(pma, mode, engine, b.dev_hay, reinterpret_cast<const uint64_t *>(b.d_off), n, 1, stream_,
                                        reinterpret_cast<daac_match16 **>(&tl.list), &tl.doc_first, &k)) != DAAC_OK) return st;
-    if ((st = tokens(b.dev_hay + b.ends[0], b.ends[1] - b.ends[0], tl, k, b.d_off, n, gap, gap_id, stream, dev_ids, dev_spans, dev_tok_offsets, n_tokens)) != DAAC_OK) return st;
-    *n_matches = k;
-    return DAAC_OK;
+    return tokens(b.dev_hay + b.ends[0], b.ends[1] - b.ends[0], tl, k, b.d_off, n, gap, gap_id, stream, o);
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // C ABI (include/daachorse_amd.h), part 13: BERT's WordPiece token ids of a word or a batch of words on the device
 // (daac_tokenize_wordpiece, daac_tokenize_wordpiece_batch).  The pieces are the tuple CSR of
 // daac_scan_batch_device16(DAAC_FIND_OVERLAPPING): its engines, refusals and max_result_bytes rule are this call's; the kernels are
-// wordpiece_kernels.hip.  This file validates its own arguments, copies the two id tables, runs the count pass, sums the counts (one
-// read-back), allocates the result and runs the write pass.  The batch arguments' rules, the staging of a host text, the length check of
-// device offsets and the single haystack as a batch of one document are the batch front door's (api_internal.hpp, "api_batch.hip").
+// wordpiece_kernels.hip.  This file holds what is the call's own: its precheck, its length limit and message, the two id tables' upload,
+// the count pass and the write pass.  The order of an entry's checks, the lattice, the scratch's layout, the sum of the counts and its
+// read-back, the limits, the result's buffers and their hand-over are the token calls' back door's (api_internal.hpp, "api_tokens.hip"),
+// which goes through the batch front door ("api_batch.hip").
 #include "api_internal.hpp"
 #include "wordpiece.hpp"
 
@@ -27,13 +28,6 @@ daac_status doc_too_long(uint64_t d, uint64_t len) {
     return DAAC_ERR_UNSUPPORTED;
 }
 
-struct Outs {   // the caller's out-pointers; the optional ones may be NULL
-    uint32_t **dev_ids;
-    uint64_t **dev_spans;
-    uint64_t **dev_tok_offsets;   // NULL: a single haystack
-    uint64_t *n_tokens, *n_matches;
-};
-
 struct Model {
     const uint32_t *first_ids, *cont_ids;
     size_t n_ids;
@@ -41,76 +35,28 @@ struct Model {
     const uint8_t *dev_skip;
 };
 
-// `dev_hay`: the haystack on the device, document 0 begins at `begin`; `len`: the bytes of all documents; `d_off`: the n + 1 offsets on
-// the device (n >= 1).  No document has 2^32 - 1 bytes or more.
-daac_status segment(daac_pma *pma, int engine, const uint8_t *dev_hay, uint64_t begin, uint64_t len, const unsigned long long *d_off, uint64_t n, hipStream_t stream,
-                    const Model &m, const Outs &o) {
-    daac_match16 *list = nullptr;
-    uint64_t *doc_first = nullptr;
-    uint64_t k = 0;
-    daac_status st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, dev_hay, reinterpret_cast<const uint64_t *>(d_off), n, 1, stream, &list, &doc_first, &k);
-    if (st != DAAC_OK) return st;
-    auto g_list = dev_guard(list, stream), g_first = dev_guard(doc_first, stream);
-
-    daac::WpArgs a{};
-    a.hay = dev_hay + begin;
-    a.seg = reinterpret_cast<const daac::WpTuple *>(list);
-    a.doc_first = reinterpret_cast<const unsigned long long *>(doc_first);
-    a.doc_off = d_off;
-    a.n_docs = n;
-    a.n_ids = m.n_ids;
-    a.unk_id = m.unk_id;
-    a.max_chars = m.max_chars;
-    a.skip = m.dev_skip;
-    // the slots (8 bytes a position), a single haystack's tok_offsets, the total, the sum's scratch, the two id tables
-    const uint64_t pos = len + n, cnt = n + 1;
-    DevBuf work;
-    HIP_TRY(work.alloc(pos * sizeof(daac::WpSlot) + (2 + cnt + exclusive_scan_scratch(cnt)) * sizeof(unsigned long long) + 2 * m.n_ids * sizeof(uint32_t), stream));
-    a.slots = static_cast<daac::WpSlot *>(work.p);
-    unsigned long long *hdr = reinterpret_cast<unsigned long long *>(a.slots + pos);
-    unsigned long long *own_off = hdr + 2;
-    unsigned long long *scan_scratch = own_off + cnt;
-    uint32_t *d_first = reinterpret_cast<uint32_t *>(scan_scratch + exclusive_scan_scratch(cnt));
-    uint32_t *d_cont = d_first + m.n_ids;
-    if (m.n_ids) {
-        HIP_TRY(hipMemcpyAsync(d_first, m.first_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_cont, m.cont_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    }
-    a.first_ids = d_first;
-    a.cont_ids = d_cont;
-
-    void *tok_off = nullptr;
-    if (o.dev_tok_offsets) HIP_TRY(dev_malloc(&tok_off, cnt * sizeof(uint64_t), stream));
-    auto g_off = dev_guard(tok_off, stream);
-    a.tok_offsets = tok_off ? static_cast<unsigned long long *>(tok_off) : own_off;
-
-    HIP_TRY(daac::launch_wordpiece_count(a, stream));
-    HIP_TRY(daac::launch_exclusive_scan(a.tok_offsets, cnt, hdr, scan_scratch, stream));
-    unsigned long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, hdr, sizeof(total), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (total > len) { set_error("the token count does not fit the text"); return DAAC_ERR_DEVICE; }   // (never seen: every token has a byte)
-    const uint64_t per_token = sizeof(uint32_t) + (o.dev_spans ? 2 * sizeof(uint64_t) : 0);
-    if (total > static_cast<uint64_t>(OPT(max_result_bytes)) / per_token) {
-        set_error("the result of " + std::to_string(total) + " tokens exceeds max_result_bytes");
-        return DAAC_ERR_AUTOMATON_SCALE;
-    }
-    void *ids = nullptr, *spans = nullptr;
-    if (total) HIP_TRY(dev_malloc(&ids, total * sizeof(uint32_t), stream));
-    auto g_ids = dev_guard(ids, stream);
-    if (total && o.dev_spans) HIP_TRY(dev_malloc(&spans, total * 2 * sizeof(uint64_t), stream));
-    auto g_spans = dev_guard(spans, stream);
-    a.ids = static_cast<uint32_t *>(ids);
-    a.spans = static_cast<unsigned long long *>(spans);
-    if (total) HIP_TRY(daac::launch_wordpiece_write(a, stream));
-    HIP_TRY(hipStreamSynchronize(stream));   // the call's scratch is released next; the result is the caller's from here
-    g_last_kernel = "wordpiece docs=" + std::to_string(n) + " matches=" + std::to_string(k) + " tokens=" + std::to_string(total) + " " + g_last_kernel;
-    *o.dev_ids = static_cast<uint32_t *>(g_ids.release());
-    if (o.dev_spans) *o.dev_spans = static_cast<uint64_t *>(g_spans.release());
-    if (o.dev_tok_offsets) *o.dev_tok_offsets = static_cast<uint64_t *>(g_off.release());
-    *o.n_tokens = total;
-    *o.n_matches = k;
-    return DAAC_OK;
+// the scratch: the slots (8 bytes a position) in front; the two id tables behind
+daac_status segment(const LatticeIn &in, const Model &m, const TokenOuts &o) {
+    const uint64_t pos = in.len + in.n;
+    hipStream_t stream = in.stream;
+    return lattice_tokens<daac::WpArgs>("wordpiece", in, pos * sizeof(daac::WpSlot), 2 * m.n_ids * sizeof(uint32_t), o,
+        [&](daac::WpArgs &a, void *front, void *behind) -> daac_status {
+            a.n_ids = m.n_ids;
+            a.unk_id = m.unk_id;
+            a.max_chars = m.max_chars;
+            a.skip = m.dev_skip;
+            a.slots = static_cast<daac::WpSlot *>(front);
+            uint32_t *d_first = static_cast<uint32_t *>(behind), *d_cont = d_first + m.n_ids;
+            if (m.n_ids) {
+                HIP_TRY(hipMemcpyAsync(d_first, m.first_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(d_cont, m.cont_ids, m.n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            }
+            a.first_ids = d_first;
+            a.cont_ids = d_cont;
+            HIP_TRY(daac::launch_wordpiece_count(a, stream));
+            return DAAC_OK;
+        },
+        [&](const daac::WpArgs &a) -> daac_status { HIP_TRY(daac::launch_wordpiece_write(a, stream)); return DAAC_OK; });
 }
 
 }  // namespace
@@ -121,23 +67,10 @@ daac_status daac_tokenize_wordpiece(daac_pma *pma, int engine, const uint8_t *ha
                                     const uint32_t *cont_ids, size_t n_ids, uint32_t unk_id, uint32_t max_chars, uint32_t **dev_ids, uint64_t **dev_spans,
                                     uint64_t *n_tokens, uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, dev_ids && n_tokens && n_matches);
-    if (st != DAAC_OK) return st;
-    if (len && !hay) { set_error("hay is NULL"); return DAAC_ERR_INVALID_ARGUMENT; }
-    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
-    if (len >= daac::kWpMaxDoc) return doc_too_long(0, len);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    DeviceTables *t = nullptr;
-    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    StagedBatch b;
-    if ((st = stage_one(hay, len, hay_is_device, stream, b)) != DAAC_OK) return st;
-    const Outs o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
+    const TokenOuts o{dev_ids, dev_spans, nullptr, n_tokens, n_matches};
     const Model m{first_ids, cont_ids, n_ids, unk_id, max_chars, nullptr};
-    return segment(pma, engine, b.dev_hay, 0, len, b.d_off, 1, stream, m, o);
+    return lattice_entry(pma, wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, o.ok(false)), engine, hay, len, hay_is_device, stream_, daac::kWpMaxDoc - 1,
+                         doc_too_long, o, [&](const LatticeIn &in) { return segment(in, m, o); });
 }
 
 daac_status daac_tokenize_wordpiece_batch(daac_pma *pma, int engine, const uint8_t *hay, const uint64_t *offsets, size_t n, int hay_is_device, void *stream_,
@@ -145,37 +78,10 @@ daac_status daac_tokenize_wordpiece_batch(daac_pma *pma, int engine, const uint8
                                           const uint8_t *dev_skip, uint32_t **dev_ids, uint64_t **dev_spans, uint64_t **dev_tok_offsets, uint64_t *n_tokens,
                                           uint64_t *n_matches) {
     PmaScope scope_(pma);
-    daac_status st = wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, dev_ids && dev_tok_offsets && n_tokens && n_matches);
-    if (st != DAAC_OK) return st;
-    if ((st = check_batch_args(hay, offsets, n, hay_is_device)) != DAAC_OK) return st;
-    if ((st = check_mode_kind(pma, DAAC_FIND_OVERLAPPING)) != DAAC_OK) return st;
-    *dev_ids = nullptr;
-    if (dev_spans) *dev_spans = nullptr;
-    *dev_tok_offsets = nullptr;
-    *n_tokens = 0;
-    *n_matches = 0;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n == 0) {   // no document: the tuple call's one offset, 0, is this call's
-        daac_match16 *list = nullptr;
-        uint64_t *doc_first = nullptr;
-        uint64_t k = 0;
-        if ((st = daac_scan_batch_device16(pma, DAAC_FIND_OVERLAPPING, engine, hay, offsets, 0, hay_is_device, stream_, &list, &doc_first, &k)) != DAAC_OK) return st;
-        *dev_tok_offsets = doc_first;
-        g_last_kernel = "wordpiece docs=0 matches=0 tokens=0 " + g_last_kernel;
-        return DAAC_OK;
-    }
-    LongDoc over;   // host offsets: before a device is looked for
-    if (!hay_is_device) (void)first_doc_over(daac::kWpMaxDoc - 1, offsets, n, nullptr, stream, over);
-    if (over) return doc_too_long(over.doc, over.len);
-    DeviceTables *t = nullptr;
-    if ((st = get_tables(pma, &t)) != DAAC_OK) return st;   // (no device: 7, before anything is staged)
-    StagedBatch b;   // a decreasing pair between the ends is the tuple call's to refuse (before the count pass)
-    if ((st = stage_batch(hay, offsets, n, hay_is_device, stream, BatchCheck::ends, b)) != DAAC_OK) return st;
-    if (hay_is_device && (st = first_doc_over(daac::kWpMaxDoc - 1, offsets, n, b.ends, stream, over)) != DAAC_OK) return st;
-    if (over) return doc_too_long(over.doc, over.len);
-    const Outs o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
+    const TokenOuts o{dev_ids, dev_spans, dev_tok_offsets, n_tokens, n_matches};
     const Model m{first_ids, cont_ids, n_ids, unk_id, max_chars, dev_skip};
-    return segment(pma, engine, b.dev_hay, b.ends[0], b.ends[1] - b.ends[0], b.d_off, n, stream, m, o);
+    return lattice_entry_batch(pma, wp_precheck(pma, first_ids, cont_ids, n_ids, max_chars, o.ok(true)), engine, hay, offsets, n, hay_is_device, stream_,
+                               "wordpiece docs=0 matches=0 tokens=0 ", daac::kWpMaxDoc - 1, doc_too_long, o, [&](const LatticeIn &in) { return segment(in, m, o); });
 }
 
 }  // extern "C"
