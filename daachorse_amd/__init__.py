@@ -10,7 +10,8 @@ from ._ffi import DaachorseError, last_engine, last_kernel, set_option
 from .bytewise import (DoubleArrayAhoCorasick, DoubleArrayAhoCorasickBuilder, Engine, Gap, Match, MatchKind, ScanMode,
                        MATCH_DTYPE, MATCH16_DTYPE, SLOT_COUNT_DTYPE, scan_count_multi,
                        Split, Splitter, char_classes, split_batch, offsets_compose, bert_char_classes, o200k_char_classes, wordpiece_tables,
-                       Norm, Normalizer, bert_normalizer, bert_normalizer_rules, SpecialTokens, splice_special)
+                       Norm, Normalizer, bert_normalizer, bert_normalizer_rules, SpecialTokens, splice_special,
+                       Packer, bert_template, roberta_template)
 from .charwise import CharwiseDoubleArrayAhoCorasick, CharwiseDoubleArrayAhoCorasickBuilder
 
 _ffi.lib()  # fail loudly at import time if the extension is missing
@@ -19,4 +20,5 @@ __all__ = ["DoubleArrayAhoCorasick", "DoubleArrayAhoCorasickBuilder", "CharwiseD
            "CharwiseDoubleArrayAhoCorasickBuilder", "Match", "MatchKind", "ScanMode", "Engine", "Gap",
            "DaachorseError", "set_option", "last_engine", "last_kernel", "MATCH_DTYPE", "MATCH16_DTYPE", "SLOT_COUNT_DTYPE", "scan_count_multi",
            "Split", "Splitter", "char_classes", "split_batch", "offsets_compose", "bert_char_classes", "o200k_char_classes",
-           "wordpiece_tables", "Norm", "Normalizer", "bert_normalizer", "bert_normalizer_rules", "SpecialTokens", "splice_special"]
+           "wordpiece_tables", "Norm", "Normalizer", "bert_normalizer", "bert_normalizer_rules", "SpecialTokens", "splice_special",
+           "Packer", "bert_template", "roberta_template"]

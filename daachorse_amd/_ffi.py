@@ -42,6 +42,23 @@ class Info(C.Structure):
                 ("plan_engine", C.c_uint8 * 8), ("plan_kernel", C.c_uint8 * 8), ("plan_reason", C.c_uint8 * 8)]
 
 
+PACK_MAX_PIECES = 16  # DAAC_PACK_MAX_PIECES
+
+
+class PackPiece(C.Structure):
+    """daac_pack_piece: kind 0 = a special token `id`, 1 = sequence A, 2 = sequence B"""
+    _fields_ = [("kind", C.c_uint32), ("id", C.c_uint32), ("type_id", C.c_uint32)]
+
+
+class PackParams(C.Structure):
+    """daac_pack_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_single", C.c_uint32), ("n_pair", C.c_uint32),
+                ("single", PackPiece * PACK_MAX_PIECES), ("pair", PackPiece * PACK_MAX_PIECES),
+                ("truncate", C.c_uint32), ("strategy", C.c_uint32), ("truncate_left", C.c_uint32), ("padding", C.c_uint32),
+                ("pad_left", C.c_uint32), ("pad_id", C.c_uint32), ("pad_type_id", C.c_uint32), ("width", C.c_uint32),
+                ("max_length", C.c_uint64), ("pad_length", C.c_uint64), ("pad_multiple", C.c_uint64)]
+
+
 ABI_VERSION = 6  # DAAC_ABI_VERSION of include/daachorse_amd.h this mirror was written against
 
 
@@ -172,6 +189,9 @@ def lib():
     L.daac_cut_batch.restype = C.c_int
     L.daac_tokens_splice.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, P(vp), P(vp), P(vp), P(C.c_uint64)]
     L.daac_tokens_splice.restype = C.c_int
+    L.daac_tokens_pack.argtypes = [P(PackParams), vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, sz, vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp),
+                                   P(C.c_uint64), P(C.c_uint64)]
+    L.daac_tokens_pack.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

@@ -713,7 +713,7 @@ class DoubleArrayAhoCorasick:
         return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_bpe_docs(self, docs, ranks=None, split=Split.Gpt2, gap=Gap.Bytes, gap_id=0, spans=False, engine=Engine.Auto, stream=None, device=False,
-                          special=None):
+                          special=None, pack=None):
         """tokenize_bpe behind a pre-tokenizer split, per document: split_batch cuts the documents into words, tokenize_bpe_batch runs over
         (hay, word_offsets) and daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or
         (ids, spans, offsets) as tokenize_bpe_batch gives them, with document i's tokens in [offsets[i], offsets[i+1]) and spans that
@@ -721,7 +721,11 @@ class DoubleArrayAhoCorasick:
         uploaded once; a word above option bpe_doc_max answers 6.  `special`: None, or a SpecialTokens: the batch is cut around the
         special tokens found in the raw text (SpecialTokens.cut_batch), the chain above runs over the segment batch, so every stretch
         of text between specials is split as a string of its own, and splice_special puts the result back together per document with
-        each special as the one token of its id.  n_matches stays the tokenizer scan's count."""
+        each special as the one token of its id.  n_matches stays the tokenizer scan's count.  `pack`: None, or a Packer: the token
+        result goes through Packer.pack as a batch of singles (its template, truncation and padding) and is freed; the call returns
+        pack's dict of planes instead."""
+        if pack is not None and not isinstance(pack, Packer):
+            raise DaachorseError(1, "pack is None or a Packer")
         b = _Batch(docs)
         if not b.is_device:
             b = _Batch(_upload(b))
@@ -731,6 +735,8 @@ class DoubleArrayAhoCorasick:
             out, k = self._bpe_docs_chain(b, sp, rk, gap, gap_id, spans, engine, stream)
         else:
             out, k = _special_docs(b, special, spans, stream, lambda sb: self._bpe_docs_chain(sb, sp, rk, gap, gap_id, spans, engine, stream))
+        if pack is not None:
+            return _pack_docs(pack, out, stream, device)
         return self._token_result(out, k, device)
 
     def _bpe_docs_chain(self, b, sp, rk, gap, gap_id, spans, engine, stream):
@@ -786,7 +792,7 @@ class DoubleArrayAhoCorasick:
         return self._token_result(o.result(), o.k.value, device)
 
     def tokenize_wordpiece_docs(self, docs, first_ids, cont_ids, unk_id, max_chars=100, split=Split.Bert, spans=False, engine=Engine.Auto, stream=None,
-                                device=False, normalizer=None, special=None):
+                                device=False, normalizer=None, special=None, pack=None):
         """tokenize_wordpiece behind BERT's pre-tokenizer, per document: split_batch cuts the documents into words, words_space tells
         which of them are whitespace, tokenize_wordpiece_batch runs over (hay, word_offsets) with those words skipped and
         daac_offsets_compose turns its offsets per word into offsets per document.  -> (ids, offsets) or (ids, spans, offsets) as
@@ -798,7 +804,11 @@ class DoubleArrayAhoCorasick:
         offsets.  `special`: None, or a SpecialTokens ([CLS], [SEP], [MASK] ..): the batch is cut around the special tokens found in
         the raw text, in front of the normalizer (SpecialTokens.cut_batch), all of the above runs over the segment batch and
         splice_special puts the result back together per document with each special as the one token of its id.  n_matches stays
-        the tokenizer scan's count."""
+        the tokenizer scan's count.  `pack`: None, or a Packer ([CLS] A [SEP], max_length, padding ..): the token result, with its
+        raw-text spans when spans=True, goes through Packer.pack as a batch of singles and is freed; the call returns pack's dict of
+        planes (input_ids, token_type_ids, attention_mask ..) instead."""
+        if pack is not None and not isinstance(pack, Packer):
+            raise DaachorseError(1, "pack is None or a Packer")
         b = _Batch(docs)
         if not b.is_device:
             b = _Batch(_upload(b))
@@ -810,6 +820,8 @@ class DoubleArrayAhoCorasick:
             out, k = self._wordpiece_docs_norm(b, sp, model, spans, engine, stream, normalizer)
         else:
             out, k = _special_docs(b, special, spans, stream, lambda sb: self._wordpiece_docs_norm(sb, sp, model, spans, engine, stream, normalizer))
+        if pack is not None:
+            return _pack_docs(pack, out, stream, device)
         return self._token_result(out, k, device)
 
     def _wordpiece_docs_norm(self, b, sp, model, spans, engine, stream, normalizer):
@@ -1348,6 +1360,181 @@ def _special_docs(b, special, spans, stream, chain):
     finally:
         for o in cut:
             o.free()
+
+
+# ---- model inputs (daac_tokens_pack): `tokenizers`' TemplateProcessing + enable_truncation + enable_padding over a token result that is
+# already in device memory: the template's special tokens around what truncation keeps, padded into the planes a model reads.
+_PACK_KINDS = {"special": 0, "a": 1, "b": 2, 0: 0, 1: 1, 2: 2}
+_PACK_STRATEGIES = {"longest_first": 0, "only_first": 1, "only_second": 2}
+_PACK_SIDES = {"right": 0, "left": 1}
+
+
+def bert_template(cls_id, sep_id):
+    """-> (single, pair): [CLS] A [SEP] and [CLS] A [SEP] B [SEP], type ids 0 for the first half and 1 for B and its [SEP]"""
+    single = [("special", cls_id, 0), ("A", 0, 0), ("special", sep_id, 0)]
+    return single, single + [("B", 0, 1), ("special", sep_id, 1)]
+
+
+def roberta_template(bos_id, eos_id):
+    """-> (single, pair): <s> A </s> and <s> A </s> </s> B </s>, every type id 0"""
+    single = [("special", bos_id, 0), ("A", 0, 0), ("special", eos_id, 0)]
+    return single, single + [("special", eos_id, 0), ("B", 0, 0), ("special", eos_id, 0)]
+
+
+class Packer:
+    """daac_tokens_pack's parameters.  `single` and `pair` are templates: lists of pieces (kind, id, type_id) with kind "special", "A" or
+    "B" (at most 16; A exactly once in each, B exactly once in `pair` and never in `single`); `single` may also be the (single, pair) of
+    bert_template() / roberta_template(), and None is the template of A alone.  `max_length`: None (no truncation) or the longest row,
+    special tokens included; `strategy` "longest_first", "only_first" or "only_second"; `truncation_side` "right" keeps a sequence's
+    first tokens, "left" its last.  `padding`: "longest", an int (rows of at least that length) or None (no padding: the CSR form);
+    `pad_to_multiple_of` rounds the row length up; `padding_side`, `pad_id`, `pad_type_id` as in `tokenizers`.  `dtype`: np.int64 or
+    np.int32, the planes' element.  The C call checks the rules and answers in the header's order."""
+
+    def __init__(self, single=None, pair=None, max_length=None, strategy="longest_first", truncation_side="right", padding="longest",
+                 pad_to_multiple_of=None, padding_side="right", pad_id=0, pad_type_id=0, dtype=np.int64):
+        if pair is None and isinstance(single, tuple) and len(single) == 2 and all(isinstance(t, list) for t in single):
+            single, pair = single
+        p = _ffi.PackParams()
+        p.struct_size = C.sizeof(_ffi.PackParams)
+        p.n_single = self._pieces(p.single, [("A", 0, 0)] if single is None else single, "single")
+        p.n_pair = self._pieces(p.pair, [] if pair is None else pair, "pair")
+        if strategy not in _PACK_STRATEGIES or truncation_side not in _PACK_SIDES or padding_side not in _PACK_SIDES:
+            raise DaachorseError(1, "strategy is longest_first, only_first or only_second, and a side is left or right")
+        if max_length is not None:
+            p.truncate, p.max_length = 1, self._u64(max_length, "max_length")
+        p.strategy, p.truncate_left, p.pad_left = _PACK_STRATEGIES[strategy], _PACK_SIDES[truncation_side], _PACK_SIDES[padding_side]
+        if padding is None:
+            p.padding = 0
+        elif isinstance(padding, str):
+            if padding != "longest":
+                raise DaachorseError(1, 'padding is "longest", a length or None')
+            p.padding = 1
+        else:
+            p.padding, p.pad_length = 2, self._u64(padding, "padding")
+        p.pad_multiple = 1 if pad_to_multiple_of is None else self._u64(pad_to_multiple_of, "pad_to_multiple_of")
+        p.pad_id, p.pad_type_id = self._u32(pad_id, "pad_id"), self._u32(pad_type_id, "pad_type_id")
+        self.dtype = np.dtype(dtype)
+        p.width = self.dtype.itemsize if self.dtype.kind in "iu" else 0   # (the C call refuses what is not 4 or 8)
+        self.params, self.csr = p, p.padding == 0
+
+    @staticmethod
+    def _u32(x, what):
+        if not 0 <= int(x) <= 0xFFFFFFFF:
+            raise DaachorseError(1, f"{what} must be in 0 .. 0xFFFFFFFF")
+        return int(x)
+
+    @staticmethod
+    def _u64(x, what):
+        if isinstance(x, bool) or not 0 <= int(x) < 1 << 64:
+            raise DaachorseError(1, f"{what} must be an integer in 0 .. 2^64 - 1")
+        return int(x)
+
+    @classmethod
+    def _pieces(cls, dst, pieces, name):
+        pieces = list(pieces)
+        if len(pieces) > _ffi.PACK_MAX_PIECES:
+            raise DaachorseError(1, f"the {name} template has {len(pieces)} pieces: at most {_ffi.PACK_MAX_PIECES}")
+        for i, pc in enumerate(pieces):
+            kind, tok, type_id = pc
+            k = _PACK_KINDS.get(kind.lower() if isinstance(kind, str) else kind)
+            if k is None:
+                raise DaachorseError(1, f'the {name} template: piece {i} is of kind {kind!r}, not "special", "A" or "B"')
+            dst[i].kind, dst[i].id, dst[i].type_id = k, cls._u32(tok, "a piece's id"), cls._u32(type_id, "a piece's type_id")
+        return len(pieces)
+
+    @staticmethod
+    def _sequence(seq, name, keep):
+        """(ids, offsets) or (ids, spans, offsets) -> (ids address, spans address or None, offsets address, tokens, documents)"""
+        if not (isinstance(seq, (tuple, list)) and len(seq) in (2, 3)):
+            raise DaachorseError(1, f"{name} is (ids, offsets) or (ids, spans, offsets)")
+        ids, spans, off = (seq[0], None, seq[1]) if len(seq) == 2 else seq
+
+        def dev(x, dtype, itemsize, what):
+            if isinstance(x, np.ndarray) or isinstance(x, (list, tuple)):
+                import torch
+                a = np.ascontiguousarray(x, dtype=dtype)
+                t = torch.from_numpy(a.view(np.int32 if itemsize == 4 else np.int64).copy()).cuda()
+                keep.append(t)
+                return (t.data_ptr() if t.numel() else None), t.numel()
+            return _device_ptr(x, itemsize, what)
+
+        p_ids, n_tok = dev(ids, np.uint32, 4, f"{name}: ids")
+        p_off, n_off = dev(off, np.uint64, 8, f"{name}: offsets")
+        p_sp = None
+        if spans is not None:
+            p_sp, n_sp = dev(spans, np.uint64, 8, f"{name}: spans")
+            if n_sp != 2 * n_tok:
+                raise DaachorseError(1, f"{name}: {n_tok} ids and {n_sp} span words: a pair a token")
+        if n_off < 1 or (n_off > 1 and not p_off):
+            raise DaachorseError(1, f"{name}: offsets hold n + 1 entries and have not been freed")
+        return p_ids if n_tok else None, p_sp if n_tok else None, p_off, n_tok, n_off - 1
+
+    def _run(self, a, b, stream):
+        """the call over device addresses -> {plane: DeviceMatches / DeviceOffsets} with .shape = (n, L), or (R,) in the CSR form"""
+        keep = []
+        a_ids, a_sp, a_off, a_tok, n = self._sequence(a, "a", keep)
+        b_ids = b_sp = b_off = None
+        b_tok = 0
+        with_spans = a_sp is not None or (len(a) == 3 and a_tok == 0)
+        if b is not None:
+            b_ids, b_sp, b_off, b_tok, n_b = self._sequence(b, "b", keep)
+            if n_b != n:
+                raise DaachorseError(1, f"a holds {n} documents and b {n_b}: a batch of pairs has one of each")
+            if n == 0 and not b_off:
+                raise DaachorseError(1, "b: offsets hold n + 1 entries and have not been freed")
+            with_spans = with_spans and (b_sp is not None or (len(b) == 3 and b_tok == 0))
+        ii, ti, am, sm, of, ro, L, slots = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokens_pack(C.byref(self.params), a_ids, a_sp, a_off, a_tok, b_ids, b_sp, b_off, b_tok, n, stream, C.byref(ii), C.byref(ti),
+                                               None if self.csr else C.byref(am), C.byref(sm), C.byref(of) if with_spans else None,
+                                               C.byref(ro) if self.csr else None, C.byref(L), C.byref(slots)))
+        del keep
+        shape = (slots.value,) if self.csr else (n, L.value)
+
+        def plane(p, dtype):
+            if self.csr:
+                m = DeviceMatches(p.value, slots.value, dtype)
+            else:   # a row an element: [n, L] through to_numpy
+                m = DeviceMatches(p.value, n if L.value else 0, np.dtype((dtype, (L.value,))) if L.value else dtype)
+            m.shape = shape + dtype.shape
+            return m
+
+        out = {"input_ids": plane(ii, self.dtype), "token_type_ids": plane(ti, self.dtype)}
+        if not self.csr:
+            out["attention_mask"] = plane(am, self.dtype)
+        out["special_tokens_mask"] = plane(sm, self.dtype)
+        if with_spans:
+            out["offsets"] = plane(of, SPAN_DTYPE)
+        if self.csr:
+            out["row_offsets"] = DeviceOffsets(ro.value, n + 1)
+        return out
+
+    @staticmethod
+    def _result(out, device):
+        if device:
+            return out
+        try:
+            return {k: v.to_numpy().reshape(v.shape) if isinstance(v, DeviceMatches) else v.to_numpy() for k, v in out.items()}
+        finally:
+            for v in out.values():
+                v.free()
+
+    def pack(self, a, b=None, stream=None, device=False):
+        """`a` and `b` are (ids, offsets) or (ids, spans, offsets) of n documents each, as the token calls return them with device=True
+        (DeviceMatches / DeviceOffsets), contiguous CUDA tensors, or numpy arrays, which are uploaded; b=None: a batch of singles.
+        -> {"input_ids", "token_type_ids", "attention_mask", "special_tokens_mask"} of shape [n, L] and, with spans, "offsets" [n, L, 2]
+        (np.uint64); without padding the planes are flat [R], there is no attention mask and "row_offsets" holds n + 1 np.uint64.
+        device=True: the same as DeviceMatches / DeviceOffsets (to_numpy / free; .shape is the plane's), left in device memory"""
+        return self._result(self._run(a, b, stream), device)
+
+
+def _pack_docs(pack, out, stream, device):
+    """what tokenize_*_docs made ([ids, spans?, doc_offsets] in device memory) through pack, the token result freed"""
+    try:
+        res = pack._run(tuple(out), None, stream)
+    finally:
+        for o in out:
+            o.free()
+    return Packer._result(res, device)
 
 
 class Norm(enum.IntEnum):

@@ -60,7 +60,9 @@ extern "C" {
  *   (6, likewise: daac_normalizer_create / daac_normalize_batch / daac_normalize and daac_spans_to_source — a per-code-point rewrite of
  *      a batch, BERT's normalizer among them, on the device.)
  *   (6, likewise: daac_cut_batch / daac_tokens_splice — a batch cut into segments around the special tokens written into its text,
- *      and a tokenizer's result over the segments put back together per document, on the device.) */
+ *      and a tokenizer's result over the segments put back together per document, on the device.)
+ *   (6, likewise: daac_tokens_pack and daac_pack_params — a token result wrapped in a template, truncated and padded into the planes a
+ *      model reads, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -835,6 +837,82 @@ daac_status daac_tokens_splice(const uint32_t *dev_ids, const uint64_t *dev_span
                                const uint32_t *dev_seg_values, const uint64_t *dev_seg_offsets, const uint64_t *dev_doc_segs,
                                const uint64_t *dev_doc_offsets, size_t n_segs, size_t n_docs, void *stream,
                                uint32_t **dev_out_ids, uint64_t **dev_out_spans, uint64_t **dev_doc_tok, uint64_t *n_tokens);
+
+/* ---- model inputs: template, truncation and padding ------------------------------------------------------------------------------------------
+ * What `tokenizers` calls the post-processor (TemplateProcessing) plus enable_truncation and enable_padding: the last step between a
+ * token result and the tensors a model reads.
+ * daac_tokens_pack.  Sequence A is a CSR token result of n documents as every token call leaves it in device memory: dev_a_ids
+ *   (a_tokens u32), dev_a_spans (a_tokens pairs of u64 relative to the document, or NULL) and dev_a_offsets (n + 1 u64).  Sequence B,
+ *   of the same n, is optional: with dev_b_offsets the whole batch is pairs, with NULL it is all singles.
+ *   Template.  params->single (n_single pieces) serves singles, params->pair (n_pair) pairs; a template has at most
+ *   DAAC_PACK_MAX_PIECES pieces {kind, id, type_id}.  DAAC_PACK_A occurs exactly once in each, DAAC_PACK_B exactly once in pair and
+ *   never in single; a DAAC_PACK_SPECIAL piece is one token.  n_added is the number of special pieces of the template in use.  n_pair
+ *   may be 0 when no B is given.
+ *   Truncation (params->truncate != 0) runs before the template, as in `tokenizers`, on budget = max_length - n_added.  With budget 0
+ *   both sequences keep 0 tokens, whatever the strategy.  A single of n1 tokens keeps min(n1, budget).  A pair with n1 + n2 <= budget
+ *   keeps all; otherwise, with need = n1 + n2 - budget: DAAC_TRUNC_LONGEST_FIRST takes the two lengths as a <= b (swapped if n1 > n2),
+ *   sets b = a if a > budget, else b = max(a, budget - a), then, if a + b > budget, a = budget / 2 and b = a + budget % 2, and swaps
+ *   back; DAAC_TRUNC_ONLY_FIRST keeps n1 - need of A and all of B, and the document is in error when n1 - need <= 0;
+ *   DAAC_TRUNC_ONLY_SECOND is the same on B.  truncate_left = 0 keeps a sequence's first tokens, 1 its last.
+ *   Rows.  A row is the template walked in order: a special piece gives (id, type_id, special 1, attention 1, span (0, 0)), a sequence
+ *   piece its kept tokens as (id, the piece's type_id, 0, 1, the token's span); a B token's span is relative to document B.
+ *   Padding.  DAAC_PAD_LONGEST, or DAAC_PAD_FIXED with pad_length: L = the longest row, or max(pad_length, longest row), rounded up to
+ *   pad_multiple (1: none).  A padding slot is (pad_id, pad_type_id, special 1, attention 0, span (0, 0)), to the right of the row or,
+ *   with pad_left = 1, to its left.  The result is dense: *dev_input_ids, *dev_token_type_ids, *dev_attention_mask and
+ *   *dev_special_tokens_mask are [n, L] planes of params->width bytes an element (4: int32, 8: int64; an id is zero-extended),
+ *   *dev_offsets is [n, L, 2] u64; *row_length = L, *n_slots = n * L.  DAAC_PAD_NONE: the result is CSR, the cu_seqlens form of
+ *   variable-length attention: the same planes as flat [R] arrays, no attention mask (*dev_attention_mask = NULL), and
+ *   *dev_row_offsets holds n + 1 u64; *row_length = the longest row, *n_slots = R.  Every plane but dev_input_ids may be NULL as an
+ *   argument: not wanted.  dev_row_offsets is written in the CSR form only (otherwise *dev_row_offsets = NULL).  A plane of no element
+ *   is NULL.  All are device memory, released with daac_device_free.  n = 0: NULL planes, L = 0 and, in the CSR form, one 0 in
+ *   row_offsets.  The call is ordered on `stream` and returns after it has finished.
+ *   Deliberate differences from `tokenizers`: max_length < n_added is status 1 (`tokenizers` silently does not truncate);
+ *   DAAC_PAD_FIXED with a longer row widens L (`tokenizers` returns a ragged batch); stride and overflowing pieces, word_ids and
+ *   sequence ids, special pieces of several ids and batches that mix singles and pairs are out of scope.
+ *   Decided before a device is touched, in this order, all status 1: a NULL params, dev_input_ids, row_length or n_slots, a NULL
+ *   dev_a_offsets with n > 0, a NULL ids list with tokens; a struct_size other than sizeof(daac_pack_params); a template that breaks
+ *   the rules above (a pair batch without a pair template included); a width other than 4 or 8; a strategy or padding outside its
+ *   enum, or a pad_multiple of 0; DAAC_TRUNC_ONLY_SECOND without B; max_length < n_added; the CSR form without dev_row_offsets;
+ *   dev_offsets without the spans of a sequence that has tokens.  Then status 2: row_offsets above the process-wide option
+ *   max_result_bytes (8 bytes a document).
+ *   After the header pass, one read-back: a document whose offsets decrease or leave [0, tokens] answers 1, and so does the first
+ *   document that ONLY_FIRST / ONLY_SECOND cannot truncate ("document <i>: ..."); nothing is handed over and every out-pointer stays
+ *   NULL.  A result above max_result_bytes (width bytes a slot and wanted plane, 16 more with offsets) answers 2 before it is
+ *   allocated.  daac_last_kernel() says "pack docs=.. pair=.. row=.. tokens=.. dropped=..".
+ *   Method: one lane per document writes a row header (what A and B keep and where) and folds the longest row, the first document in
+ *   error, the slots and the dropped tokens into four words, a wave reduction and one atomic per wave; CSR: the rows' lengths are
+ *   summed to row_offsets; one lane per output slot of the flat n * L (or R) index space finds its row and column, its source —
+ *   padding, a template piece, a token of A or B — and stores that slot of every plane: 64 consecutive elements per wave, no atomics.
+ *   Scratch: 32 bytes a document. */
+typedef enum { DAAC_PACK_SPECIAL = 0, DAAC_PACK_A = 1, DAAC_PACK_B = 2 } daac_pack_piece_kind;
+typedef enum { DAAC_TRUNC_LONGEST_FIRST = 0, DAAC_TRUNC_ONLY_FIRST = 1, DAAC_TRUNC_ONLY_SECOND = 2 } daac_pack_strategy;
+typedef enum { DAAC_PAD_NONE = 0, DAAC_PAD_LONGEST = 1, DAAC_PAD_FIXED = 2 } daac_pack_padding;
+#define DAAC_PACK_MAX_PIECES 16
+typedef struct {
+    uint32_t kind;      /* daac_pack_piece_kind */
+    uint32_t id;        /* DAAC_PACK_SPECIAL: the token */
+    uint32_t type_id;
+} daac_pack_piece;
+typedef struct {
+    uint32_t struct_size;   /* sizeof(daac_pack_params) */
+    uint32_t n_single, n_pair;
+    daac_pack_piece single[DAAC_PACK_MAX_PIECES], pair[DAAC_PACK_MAX_PIECES];
+    uint32_t truncate;      /* 0: no truncation (strategy, truncate_left and max_length are not read) */
+    uint32_t strategy;      /* daac_pack_strategy */
+    uint32_t truncate_left;
+    uint32_t padding;       /* daac_pack_padding */
+    uint32_t pad_left;
+    uint32_t pad_id, pad_type_id;
+    uint32_t width;         /* 4 or 8 */
+    uint64_t max_length;
+    uint64_t pad_length;    /* DAAC_PAD_FIXED */
+    uint64_t pad_multiple;  /* 1: none */
+} daac_pack_params;
+daac_status daac_tokens_pack(const daac_pack_params *params, const uint32_t *dev_a_ids, const uint64_t *dev_a_spans, const uint64_t *dev_a_offsets,
+                             uint64_t a_tokens, const uint32_t *dev_b_ids, const uint64_t *dev_b_spans, const uint64_t *dev_b_offsets,
+                             uint64_t b_tokens, size_t n, void *stream, void **dev_input_ids, void **dev_token_type_ids,
+                             void **dev_attention_mask, void **dev_special_tokens_mask, uint64_t **dev_offsets, uint64_t **dev_row_offsets,
+                             uint64_t *row_length, uint64_t *n_slots);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

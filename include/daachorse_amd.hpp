@@ -502,4 +502,21 @@ using DoubleArrayAhoCorasickBuilder = BasicBuilder<detail::Bytewise>;
 using CharwiseDoubleArrayAhoCorasick = BasicAhoCorasick<detail::Charwise>;
 using CharwiseDoubleArrayAhoCorasickBuilder = BasicBuilder<detail::Charwise>;
 
+// daac_tokens_pack over a batch of singles in device memory (template, truncation and padding: the header has the definition): the
+// planes stay on the device and are the caller's, released with daac_device_free.  -> {row length, slots}
+struct PackedPlanes {
+    void *input_ids = nullptr, *token_type_ids = nullptr, *attention_mask = nullptr, *special_tokens_mask = nullptr;
+    uint64_t *offsets = nullptr, *row_offsets = nullptr;
+    uint64_t row_length = 0, slots = 0;
+};
+inline PackedPlanes tokens_pack(const daac_pack_params &params, const uint32_t *dev_ids, const uint64_t *dev_spans, const uint64_t *dev_offsets, uint64_t n_tokens,
+                                size_t n, void *stream = nullptr) {
+    PackedPlanes r;
+    const daac_status st = daac_tokens_pack(&params, dev_ids, dev_spans, dev_offsets, n_tokens, nullptr, nullptr, nullptr, 0, n, stream, &r.input_ids, &r.token_type_ids,
+                                            params.padding == DAAC_PAD_NONE ? nullptr : &r.attention_mask, &r.special_tokens_mask, dev_spans ? &r.offsets : nullptr,
+                                            params.padding == DAAC_PAD_NONE ? &r.row_offsets : nullptr, &r.row_length, &r.slots);
+    if (st != DAAC_OK) throw PanicError(std::string("tokens_pack failed: ") + daac_last_error());
+    return r;
+}
+
 }  // namespace daachorse

@@ -49,6 +49,35 @@ pub struct daac_shard {
     pub len: usize,
     pub base: u64,
 }
+/// a piece of a daac_tokens_pack template: kind 0 = the special token `id`, 1 = sequence A, 2 = sequence B
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct daac_pack_piece {
+    pub kind: u32,
+    pub id: u32,
+    pub type_id: u32,
+}
+/// daac_tokens_pack's parameters (include/daachorse_amd.h: daac_pack_params); struct_size = size_of::<daac_pack_params>()
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct daac_pack_params {
+    pub struct_size: u32,
+    pub n_single: u32,
+    pub n_pair: u32,
+    pub single: [daac_pack_piece; 16],
+    pub pair: [daac_pack_piece; 16],
+    pub truncate: u32,
+    pub strategy: u32, //      0 longest_first, 1 only_first, 2 only_second
+    pub truncate_left: u32,
+    pub padding: u32, //       0 none (CSR), 1 longest, 2 fixed (pad_length)
+    pub pad_left: u32,
+    pub pad_id: u32,
+    pub pad_type_id: u32,
+    pub width: u32, //         4 or 8
+    pub max_length: u64,
+    pub pad_length: u64,
+    pub pad_multiple: u64, //  1: none
+}
 #[repr(C)]
 pub struct daac_pma {
     _p: [u8; 0],
@@ -139,6 +168,13 @@ extern "C" {
     pub fn daac_tokenize_bpe_batch(pma: *mut daac_pma, engine: i32, hay: *const u8, offsets: *const u64, n: usize, hay_is_device: i32,
                                    stream: *mut c_void, ranks: *const u32, n_ranks: usize, gap: i32, gap_id: u32, dev_ids: *mut *mut u32,
                                    dev_spans: *mut *mut u64, dev_tok_offsets: *mut *mut u64, n_tokens: *mut u64, n_matches: *mut u64) -> i32;
+    /// a token result (ids, optional spans, n + 1 offsets; a second sequence makes the batch pairs) wrapped in the template, truncated and
+    /// padded into the planes a model reads: [n, L] planes of `width` bytes an element, or flat planes and row offsets without padding
+    pub fn daac_tokens_pack(params: *const daac_pack_params, dev_a_ids: *const u32, dev_a_spans: *const u64, dev_a_offsets: *const u64, a_tokens: u64,
+                            dev_b_ids: *const u32, dev_b_spans: *const u64, dev_b_offsets: *const u64, b_tokens: u64, n: usize, stream: *mut c_void,
+                            dev_input_ids: *mut *mut c_void, dev_token_type_ids: *mut *mut c_void, dev_attention_mask: *mut *mut c_void,
+                            dev_special_tokens_mask: *mut *mut c_void, dev_offsets: *mut *mut u64, dev_row_offsets: *mut *mut u64,
+                            row_length: *mut u64, n_slots: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
