@@ -1,6 +1,7 @@
 // What the translation units of the C ABI share (include/daachorse_amd.h; api_upload.hip, api_scan.hip, api_select.hip, api_iter.hip,
-// api_options.hip): the options, the handle, its device tables, the call-scoped buffers and the drivers one unit calls in another.
-// Internal: nothing here is exported.
+// api_options.hip, api_batch.hip, api_tokens.hip, api_hist.hip, api_replace.hip, api_cut.hip, api_split.hip, api_normalize.hip,
+// api_tokenize.hip, api_unigram.hip, api_bpe.hip, api_wordpiece.hip, api_pack.hip): the options, the handle, its device tables, the
+// call-scoped buffers and the drivers one unit calls in another.  Internal: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,15 +22,7 @@
 #include <utility>
 #include <vector>
 
-#include "charwise.hpp"
-#include "device_tables.hpp"
-#include "gram.hpp"
-#include "gram2.hpp"
-#include "gram4.hpp"
-#include "gram2w.hpp"
-#include "pfx.hpp"
-#include "pma.hpp"
-#include "repack.hpp"
+#include "upload_layout.hpp"   // EngineTables; with it device_tables.hpp and the builders' headers
 
 namespace daac {
 const char *last_error_cstr();
@@ -204,47 +197,21 @@ struct DevBuf {  // scratch that lives as long as the call
 };
 
 // ----------------------------------------------------------------------------- device tables
-struct DeviceTables {
+// A handle's state on one device: what the upload computed (EngineTables, upload_layout.hpp) and what the scans keep beside it at run time.
+struct DeviceTables : EngineTables {
     int device = -1;
     int num_cu = 0;
     std::vector<void *> allocs;
-    bool tier_ok = false;
-    TierDev tier{};
-    DArrayDev da{};
-    TierTables tier_host_meta;  // sizes only (vectors cleared after upload)
-    bool gram_ok = false;
-    GramDev gram{};
-    bool gram2_ok = false;     // second table set (gram2.hpp)
-    Gram2Dev gram2{};
-    bool gram4_ok = false;     // `.count()` tables of round 5 (gram4.hpp), derived from the second table set
-    Gram4Dev gram4{};
-    bool gramw_ok = false;     // wide alphabets (gram2w.hpp)
-    bool pfx_ok = false;       // any byte alphabet, `.count()` (pfx.hpp)
-    uint32_t n_distinct_bytes = 0;  // distinct pattern bytes (known when the PFX builder ran)
-    PfxDev pfx{};
-    Gram2WDev gramw{};
-    Gram2EmitDev emit{};
-    bool emit3_ok = false;     // ... with detection done once (emit3_kernels.hip)
-    Gram3Lds emit3_lds{};
-    bool emit3_has_len1 = false;   // some pattern is a single byte
-    const uint32_t *pfx_probe_word = nullptr;   // device word the probe kernel leaves its count in
     std::atomic<int> pfx_dense{-1};  // the last probe's verdict on the text (scan_count_impl): 1 = most positions survive the filter
-    bool find3_ok = false;         // find_iter's count / checksum without a state chain (find3_kernels.hip): K = 3, no pattern beyond 19 bytes
-    Find3Dev find3{};
-    Find3Dev find3v{};             // the same tables with the patterns' VALUES (the emitter's V1 / V2 / V3 rank structure): the selection's tuple list
-    bool left3_ok = false;         // a leftmost handle whose patterns, as a Standard automaton, got the emitter's and find3's tables: left3_kernels.hip serves leftmost_find_iter
     std::atomic<uint32_t> find3_gave_up{0};
     std::atomic<uint32_t> find3_retry{0}, emit3_retry{0};   // large requests turned away since the engines gave up (every sixteenth tries again)
     std::atomic<uint32_t> find3_skips{0};
     std::atomic<uint32_t> find3_rec_per_kib{0};   // deep matches per KiB the last find3 request met, + 1 (0: none yet): text made of the dictionary's
                                                    // own words keeps DETECT's walkers busy (3.4 ms per GiB against 1.4) and the chain walkers are faster there
-    bool pfx_emit_ok = false;      // PFX tuples: pfx_emit_kernel + EXPAND over the raw haystack (no pattern registered twice)
-    Gram2EmitDev pfx_emit{};       // what that EXPAND needs: V1 by byte + the 256 flag bytes (v1, v1_bytes = 1280), K = 1
     std::atomic<uint32_t> emit3_rec_per_kib{0};  // deep-match records per KiB the last scans met (sizes the next scan's list)
     // scans in a row on which an emitter gave up on the TEXT (more deep matches or extras than it places: known only after its detection
     // has run): from the second on the handle stops trying and the plan says so (a served scan resets the count)
     std::atomic<uint32_t> emit3_gave_up{0};
-    CharDev chr{};  // charwise automata only
     // The emitter's and find3's scratch (annotated stream, record list, scan arrays: ~2 bytes per haystack byte), kept by the handle from
     // one call to the next — the stream-ordered pool's calls cost host time in proportion to the bytes asked for, and what a call frees is
     // handed back at the next synchronisation (tools/micro/pool_ops.hip: 0.3 + 0.45 ms per GiB).  One call at a time borrows it
@@ -258,6 +225,7 @@ struct DeviceTables {
         for (void *p : allocs) (void)hipFree(p);
         if (ws_p) (void)hipFree(ws_p);
     }
+    // the layout layer's device sink
     template <class T>
     daac_status put(const std::vector<T> &v, const T *&out) {
         // padded so that 16-byte granule copies into LDS never run past the allocation
@@ -388,7 +356,7 @@ struct daac_matches {
 };
 
 
-// ---- what the translation units of the C ABI share (api_upload.hip, api_scan.hip, api_select.hip, api_iter.hip, api_options.hip)
+// ---- the drivers one translation unit of the C ABI calls in another
 namespace daac {
 namespace api {
 

@@ -242,7 +242,11 @@ struct Gram4Lds {
 };
 // the LDS the filter's Bloom array may take at the preferred launch shape (32 positions per lane, 16 waves, coarse directory — `sdir_bytes`;
 // the displacement table's bytes in its place where the perfect hash was built): what build_gram4_filter is given at upload
-uint32_t gram4_filter_room(uint32_t m_bytes, uint32_t sdir_bytes, bool arith, uint32_t lds_limit);
+constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the LDS address of the byte three before the hit byte
+inline uint32_t gram4_filter_room(uint32_t m_bytes, uint32_t sdir_bytes, bool arith, uint32_t lds_limit) {
+    const uint32_t fixed = 16u * kList4 * 2u + 16u * (64u * 32u + 32u) + (arith ? 0u : 256u) + sdir_bytes + m_bytes;
+    return fixed < lds_limit ? (lds_limit - fixed) & ~15u : 0u;
+}
 bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, bool want_arith, bool want_filter, uint32_t lds_limit, Gram4Lds &L);
 hipError_t launch_gram4_scan(const Gram4Dev &dev, const GramArgs &a, const Gram4Lds &L, uint32_t blocks, hipStream_t stream);
 
@@ -292,7 +296,19 @@ struct Expand3Args {
     unsigned int *fail;                  // bit 2: more extras in one tile than EXPAND places; bit 3: a slot outside its tile (a bug)
     uint32_t vlen, emit_from;            // RAW (PFX) only: `ann` is the haystack; positions in [emit_from, vlen) can end a one-byte match
 };
-bool emit3_plan(const Gram2EmitDev &dev, uint32_t waves, uint32_t lds_limit, Gram3Lds &L);
+constexpr uint32_t kRingE3 = 128;        // entries of a wave's hit queue (FIFO; at most 63 left over + 64 new)
+constexpr uint32_t kOffME3 = 256;        // LDS offset of ME (classes at 0)
+inline bool emit3_plan(const Gram2EmitDev &dev, uint32_t waves, uint32_t lds_limit, Gram3Lds &L) {
+    L = Gram3Lds{};
+    const uint32_t slot = 64u * 32u + 32u;
+    L.wave_stride = 2u * slot + kRingE3 * 4u;
+    L.off_s = kOffME3 + dev.m_bytes;
+    L.off_wave = L.off_s + dev.s_bytes;
+    L.lds_bytes = L.off_wave + waves * L.wave_stride;
+    L.threads = waves * 64u;
+    L.rfull = 0;
+    return L.lds_bytes <= lds_limit;
+}
 hipError_t launch_emit3_detect(const Gram2EmitDev &dev, const Emit3Args &a, const Gram3Lds &L, uint32_t blocks, hipStream_t stream);
 hipError_t launch_emit3_combine(const uint32_t *tile_short, const uint32_t *tile_deep, unsigned long long *total, unsigned long long *deep, uint64_t n,
                                 hipStream_t stream);
@@ -300,7 +316,9 @@ hipError_t launch_emit3_bin(const uint4 *recs, const uint32_t *chunk_fill, const
                             uint32_t *cursor, uint4 *binned, uint32_t n1k, unsigned long long rec_limit, uint32_t blocks, hipStream_t stream);
 hipError_t launch_emit3_expand(const Gram2EmitDev &dev, const Expand3Args &a, bool f16, uint32_t blocks, hipStream_t stream);
 hipError_t launch_emit3_expand_raw(const Gram2EmitDev &dev, const Expand3Args &a, bool f16, uint32_t blocks, hipStream_t stream);
-uint32_t emit3_expand_lds_bytes(const Gram2EmitDev &dev, uint32_t waves, bool f16, bool v3_in_lds);
+inline uint32_t emit3_expand_lds_bytes(const Gram2EmitDev &dev, uint32_t waves, bool f16, bool v3_in_lds) {
+    return dev.v1_bytes + dev.v2_bytes + (v3_in_lds ? dev.v3c_bytes : 0u) + waves * (f16 ? kEmit3ExpandWave16 : kEmit3ExpandWave);
+}
 
 // PFX engine (pfx.hpp): `.count()` for bytewise automata over any byte alphabet.  LDS: BLOOM at 0 | DISP | CNT1 | per-wave areas
 // find_iter without a state chain (find3_kernels.hip): SELECT over the emitter's annotated stream and binned records.
@@ -344,13 +362,13 @@ struct Find3Args {
 __device__ __forceinline__ bool find3_detect_usable(const Find3Args &a) {
     return a.ctl[0] <= a.chunk_cap && a.ctl[1] == 0u && a.bin_off[a.n1k] <= a.rec_limit;
 }
-uint32_t find3_lds_bytes(const Find3Dev &dev, bool tally);
+inline uint32_t find3_lds_bytes(const Find3Dev &dev, bool tally) { return (tally ? dev.h1_bytes + dev.h2_bytes + dev.h3c_bytes : 0u) + 16u * kFind3Wave; }
 hipError_t launch_find3_select(const Find3Dev &dev, const Find3Args &a, bool has_len1, bool tally, uint32_t blocks, hipStream_t stream);
 hipError_t launch_find3_emit(const Find3Dev &dev, const Find3Args &a, bool has_len1, uint32_t blocks, hipStream_t stream);
 hipError_t launch_left3_emit(const Find3Dev &dev, const Find3Args &a, bool has_len1, uint32_t blocks, hipStream_t stream);
 hipError_t launch_find3_tail(const Find3Args &a, bool has_len1, uint32_t blocks, hipStream_t stream);
 // leftmost_find_iter likewise (left3_kernels.hip): exit_out / entry_in hold, per tile, how many positions of the NEXT tile lie under its last match
-uint32_t left3_lds_bytes(const Find3Dev &dev, bool tally);
+inline uint32_t left3_lds_bytes(const Find3Dev &dev, bool tally) { return (tally ? dev.h1_bytes + dev.h2_bytes + dev.h3c_bytes : 0u) + 16u * kLeft3Wave; }
 hipError_t launch_left3_tail(const Find3Args &a, bool has_len1, uint32_t blocks, hipStream_t stream);
 hipError_t launch_left3_select(const Find3Dev &dev, const Find3Args &a, bool has_len1, bool tally, uint32_t blocks, hipStream_t stream);
 
@@ -369,7 +387,17 @@ struct PfxDev {
     uint32_t off_disp, off_cnt1, off_wave, wave_stride, lds_bytes, threads;   // pfx_plan
     uint32_t n_keys;
 };
-bool pfx_plan(PfxDev &d, uint32_t lds_limit);
+constexpr uint32_t kRingP = 128;     // entries of a wave's survivor queue (FIFO; at most 63 left over + 64 new)
+// LDS plan: BLOOM at 0, DISP, CNT1, then 16 waves x (two text slots + the survivor queue)
+inline bool pfx_plan(PfxDev &d, uint32_t lds_limit) {
+    d.off_disp = d.bloom_bytes;
+    d.off_cnt1 = d.off_disp + d.disp_bytes;
+    d.off_wave = d.off_cnt1 + 512u + 1024u;   // CNT1 (u16 x 256), then the h32 sums of the one-byte patterns (u32 x 256, count + checksum only)
+    d.wave_stride = 2u * (1024u + 32u) + kRingP * 4u;
+    d.lds_bytes = d.off_wave + 16u * d.wave_stride;
+    d.threads = 1024;
+    return d.lds_bytes <= lds_limit;
+}
 hipError_t launch_pfx_scan(const PfxDev &dev, const GramArgs &a, bool exact, uint32_t blocks, hipStream_t stream);
 hipError_t launch_pfx_probe(const PfxDev &dev, const uint8_t *hay, uint64_t len, unsigned int *out, hipStream_t stream);
 struct Emit3Args;

@@ -35,8 +35,6 @@ namespace daac {
 namespace {
 
 typedef uint32_t e3_u32x4_t __attribute__((ext_vector_type(4)));
-constexpr uint32_t kRingE3 = 128;        // entries of a wave's hit queue (FIFO; at most 63 left over + 64 new)
-constexpr uint32_t kOffME3 = 256;        // LDS offset of ME (classes at 0)
 constexpr uint32_t kContBitsE3 = 0x1ffffffeu;  // continuation bits of an ME word (classes 1 .. 28)
 typedef __attribute__((address_space(3))) const uint32_t ldsx_cu32;
 typedef __attribute__((address_space(3))) uint32_t ldsx_u32;
@@ -1047,18 +1045,6 @@ __global__ __launch_bounds__((F16 && !RAW) ? 512 : 256, (F16 && !RAW) ? 4 : 3) v
 }
 
 // ================================================================================================================ launchers
-bool emit3_plan(const Gram2EmitDev &dev, uint32_t waves, uint32_t lds_limit, Gram3Lds &L) {
-    L = Gram3Lds{};
-    const uint32_t slot = 64u * 32u + 32u;
-    L.wave_stride = 2u * slot + kRingE3 * 4u;
-    L.off_s = kOffME3 + dev.m_bytes;
-    L.off_wave = L.off_s + dev.s_bytes;
-    L.lds_bytes = L.off_wave + waves * L.wave_stride;
-    L.threads = waves * 64u;
-    L.rfull = 0;
-    return L.lds_bytes <= lds_limit;
-}
-
 template <int K, bool S16>
 static hipError_t launch_detect_inst(const Gram2EmitDev &dev, const Emit3Args &a, const Gram3Lds &L, uint32_t blocks, hipStream_t stream) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(emit3_detect_kernel<K, S16>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1082,10 +1068,6 @@ hipError_t launch_emit3_bin(const uint4 *recs, const uint32_t *chunk_fill, const
                             uint32_t *cursor, uint4 *binned, uint32_t n1k, unsigned long long rec_limit, uint32_t blocks, hipStream_t stream) {
     hipLaunchKernelGGL(emit3_bin_kernel, dim3(blocks), dim3(256), 0, stream, recs, chunk_fill, chunk_next, chunk_cap, bin_off, cursor, binned, n1k, rec_limit);
     return hipGetLastError();
-}
-
-uint32_t emit3_expand_lds_bytes(const Gram2EmitDev &dev, uint32_t waves, bool f16, bool v3_in_lds) {
-    return dev.v1_bytes + dev.v2_bytes + (v3_in_lds ? dev.v3c_bytes : 0u) + waves * (f16 ? kEmit3ExpandWave16 : kEmit3ExpandWave);
 }
 
 template <int K, bool F16, bool HAS1, bool RAW>

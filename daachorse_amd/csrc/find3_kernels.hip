@@ -524,7 +524,6 @@ __global__ __launch_bounds__(256) void find3_tail_kernel(const Find3Args a) {
     }
 }
 
-uint32_t find3_lds_bytes(const Find3Dev &dev, bool tally) { return (tally ? dev.h1_bytes + dev.h2_bytes + dev.h3c_bytes : 0u) + 16u * kFind3Wave; }
 
 hipError_t launch_find3_tail(const Find3Args &a, bool has_len1, uint32_t blocks, hipStream_t stream) {
     if (has_len1) hipLaunchKernelGGL(find3_tail_kernel<true>, dim3(blocks), dim3(256), 0, stream, a);

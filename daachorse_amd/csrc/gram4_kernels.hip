@@ -68,7 +68,6 @@ namespace daac {
 namespace {
 
 typedef uint32_t g4_u32x4_t __attribute__((ext_vector_type(4)));
-constexpr uint32_t kList4 = 256;        // entries of a wave's hit list (linear; a step's hits beyond it wait for the next pass), u16 each: the LDS address of the byte three before the hit byte
 // batches of a pass of the FILT body at 32 / 16 positions per lane (round 13).  A pass keeps position, key bytes and text of each of its batches
 // in registers: at 16 positions per lane that would cost the 64 VGPRs and with them the second workgroup of a CU, so those instances keep one
 constexpr int kPass4Q2 = 2, kPass4Q1 = 1;
@@ -1086,10 +1085,6 @@ bool gram4_plan(const Gram4Dev &dev, uint32_t ppl, uint32_t waves, bool rfull, b
     L.off_m = L.off_s + region;
     L.lds_bytes = L.off_m + dev.m_bytes;
     return L.lds_bytes <= lds_limit;
-}
-uint32_t gram4_filter_room(uint32_t m_bytes, uint32_t sdir_bytes, bool arith, uint32_t lds_limit) {
-    const uint32_t fixed = 16u * kList4 * 2u + 16u * (64u * 32u + 32u) + (arith ? 0u : 256u) + sdir_bytes + m_bytes;
-    return fixed < lds_limit ? (lds_limit - fixed) & ~15u : 0u;
 }
 
 // a.sel_want: 0 = plain records, 1 = tail records from the hit record on, 2 = every workgroup decides by its density probe

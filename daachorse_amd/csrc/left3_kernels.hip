@@ -537,7 +537,6 @@ hipError_t launch_left3_tail(const Find3Args &a, bool has_len1, uint32_t blocks,
     return hipGetLastError();
 }
 
-uint32_t left3_lds_bytes(const Find3Dev &dev, bool tally) { return (tally ? dev.h1_bytes + dev.h2_bytes + dev.h3c_bytes : 0u) + 16u * kLeft3Wave; }
 
 template <bool HAS1, bool TALLY, bool EMIT>
 static hipError_t launch_left3_inst(const Find3Dev &dev, const Find3Args &a, uint32_t blocks, hipStream_t stream) {

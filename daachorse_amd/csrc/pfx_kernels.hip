@@ -25,7 +25,6 @@ namespace daac {
 namespace {
 
 typedef uint32_t px_u32x4_t __attribute__((ext_vector_type(4)));
-constexpr uint32_t kRingP = 128;     // entries of a wave's survivor queue (FIFO; at most 63 left over + 64 new)
 typedef __attribute__((address_space(3))) const uint32_t ldsp_cu32;
 typedef __attribute__((address_space(3))) uint32_t ldsp_u32;
 typedef __attribute__((address_space(3))) const uint16_t ldsp_cu16;
@@ -747,17 +746,6 @@ __global__ __launch_bounds__(1024) void pfx_probe_kernel(const PfxDev g, const u
 hipError_t launch_pfx_probe(const PfxDev &dev, const uint8_t *hay, uint64_t len, unsigned int *out, hipStream_t stream) {
     hipLaunchKernelGGL(pfx_probe_kernel, dim3(1), dim3(1024), 0, stream, dev, hay, len, out);
     return hipGetLastError();
-}
-
-// LDS plan: BLOOM at 0, DISP, CNT1, then 16 waves x (two text slots + the survivor queue)
-bool pfx_plan(PfxDev &d, uint32_t lds_limit) {
-    d.off_disp = d.bloom_bytes;
-    d.off_cnt1 = d.off_disp + d.disp_bytes;
-    d.off_wave = d.off_cnt1 + 512u + 1024u;   // CNT1 (u16 x 256), then the h32 sums of the one-byte patterns (u32 x 256, count + checksum only)
-    d.wave_stride = 2u * (1024u + 32u) + kRingP * 4u;
-    d.lds_bytes = d.off_wave + 16u * d.wave_stride;
-    d.threads = 1024;
-    return d.lds_bytes <= lds_limit;
 }
 
 hipError_t launch_pfx_scan(const PfxDev &dev, const GramArgs &a, bool exact, uint32_t blocks, hipStream_t stream) {

@@ -1,6 +1,6 @@
 // Host-side helper of tests/test_gpu_gram4_survivors.py (no GPU needed): walks a text as gram4's FILT body walks it and writes, for every hit
 // in text order — a (K+1)-gram ending at byte p that is a trie prefix —, one u32: p | passed << 31, where `passed` is the probe of
-// gram4_filter.hpp against the Bloom array.  The tables are built as the upload builds them (api_upload.hip: the table budget less the hit
+// gram4_filter.hpp against the Bloom array.  The tables are built as the upload builds them (upload_layout.hpp, gram2 and gram4: the table budget less the hit
 // rings, the perfect hash first when asked for, the Bloom array in the room gram4_filter_room leaves less 512 bytes), so the array is the
 // one the kernel stages.
 //   usage: gram4_survivors_check <blob> <haystack-file> <mph: 0 | 1> <out-file>

@@ -254,8 +254,8 @@ ENGINE_CASES = {
 @pytest.mark.parametrize("case", list(ENGINE_CASES))
 def test_full_range_values(values_case, case):
     """values over the whole u32 range through every engine: the emitter's {p, len | copy << 24, value} records (emit3_kernels.hip:157), the
-    v1 / v2 / v3 value tables and the v3c rank blob (api_upload.hip:433-470), find3 / left3's match_hash32(value, len) tables
-    (api_upload.hip:473-487), gram4's inline h, the TIERED / DARRAY output lists and the checksum's mix64(value << 32 | length)"""
+    v1 / v2 / v3 value tables and the v3c rank blob (upload_layout.hpp, emitter and emitter_rank_tables), find3 / left3's match_hash32(value, len)
+    tables (emitter_rank_tables), gram4's inline h, the TIERED / DARRAY output lists and the checksum's mix64(value << 32 | length)"""
     pats, vals, host = values_case
     opts, engine, kernel = ENGINE_CASES[case]
     forced = engine != Engine.Auto
@@ -331,7 +331,7 @@ LENGTH_CUTS = [c for c in range(0, 1 << 20, 2048)]
 @pytest.mark.parametrize("case", ["auto", "tiered", "darray", "pfx", "emit0", "gram_v4"])
 def test_long_patterns(lengths_case, case):
     """patterns at every packing edge up to 65 537 bytes, nested with their prefixes and suffixes, planted across cuts: emit3's staged
-    {position | length << 10} and 24-bit lengths (api_upload.hip:492), gram2's patterns longer than K + 16 (gram2.hpp:61) and tail records
+    {position | length << 10} and 24-bit lengths (upload_layout.hpp, emitter: `fits`), gram2's patterns longer than K + 16 (gram2.hpp:61) and tail records
     (gram2.cpp:187), the compact iterator's / stepper's 32 - bits(max_len) end bits, and batches entering a piece min(halo, rel) bytes
     early with halos longer than a piece (batch_piece 256 and the default)"""
     K, pats, vals, host = lengths_case
@@ -391,7 +391,7 @@ def test_long_patterns_batch_piece(lengths_case):
 
 @pytest.mark.parametrize("max_len,served", [(19, True), (20, False)])
 def test_find3_length_gate(max_len, served):
-    """find3's tables exist only for max_len <= 19 (api_upload.hip:473); it stages {position | length << 11} and tests (r.y & 0xffffff) < 32
+    """find3's tables exist only for max_len <= 19 (upload_layout.hpp, emitter_rank_tables); it stages {position | length << 11} and tests (r.y & 0xffffff) < 32
     (find3_kernels.hip:337): at 19 bytes find3 / left3 serve, at 20 they decline to the chain walkers, with the oracle's answer either way"""
     K = _k_of_words()
     pats, vals, text = synth.patterns_lengths(K, max_len=max_len)
@@ -417,7 +417,7 @@ def test_find3_length_gate(max_len, served):
 
 @pytest.mark.parametrize("L,emits", [((1 << 22) - 1, True), (1 << 22, False)])
 def test_emitter_length_gate(L, emits):
-    """emit3 keeps a staged tuple's length in 22 bits: gated off at max_len >= 2^22 (api_upload.hip:492, PFX's emitter at :574); one pattern of
+    """emit3 keeps a staged tuple's length in 22 bits: gated off at max_len >= 2^22 (upload_layout.hpp, emitter: `fits`; PFX's emitter in pfx: pfx_emit_ok); one pattern of
     2^22 - 1 bytes goes through the emitter, one of 2^22 bytes to the fallback, and both give the oracle's tuples"""
     pats, vals, text = synth.patterns_single_long(L)
     host = _host(text)
@@ -452,7 +452,7 @@ def test_copies(n_copies):
     """one long pattern registered n times with its own value per copy.  The emitter keeps a state's further copies in 8 bits (erec.w >> 24,
     gram2.cpp:271, up to 256 copies at gram2.cpp:236), but EXPAND places each further copy as an extra at the position where the pattern
     ends, counts a position's extras in 4 bits (emit3_kernels.hip:741) and takes 64 per tile (:719).  The upload gate on the copies
-    (api_upload.hip, max_copies <= kEmit3MaxExtrasAtPosition) gives the emitter 16 copies and sends 17 and more to the segment scanners from
+    (upload_layout.hpp, emitter: max_copies <= kEmit3MaxExtrasAtPosition) gives the emitter 16 copies and sends 17 and more to the segment scanners from
     the start; a pattern of <= K bytes registered twice goes there always.  Where the plan names the emitter it must really serve the list
     (daac_last_engine): with 2 copies on dense text, with 16 on text that holds the pattern once per 2 KiB (15 extras per tile).  Copies
     come out in registration order (the crate's per-end output order); find_iter / leftmost report the first copy."""
@@ -471,7 +471,7 @@ def test_copies(n_copies):
         info = p.info()
         if emits:
             assert info.plan_kernel[2] == K_EMIT, (n_copies, p.explain())
-        else:   # regression: the copies gate (api_upload.hip, max_copies <= kEmit3MaxExtrasAtPosition) / the short-duplicate gate (gram2.cpp:236)
+        else:   # regression: the copies gate (upload_layout.hpp, emitter: max_copies <= kEmit3MaxExtrasAtPosition) / the short-duplicate gate (gram2.cpp:236)
             fallback = _tuples_fall_back(info, 2, ("copies gate", n_copies, len(sel)))
             assert info.plan_reason[2] == 5, list(info.plan_reason)   # DAAC_WHY_DUPLICATES
         served = _all_kinds(ps, vs, host, cuts=[4096, 20000])
@@ -489,7 +489,7 @@ def test_copies(n_copies):
 @pytest.mark.parametrize("n_outputs", [65535, 65536])
 def test_charwise_output_layouts(n_outputs):
     """the charwise walker records keep output_pos in 16 bits + a 16-bit child filter below 65 536 outputs and 24 + 8 bits below 2^24
-    (api_upload.hip:130): 65 535 outputs is the last of the first layout, 65 536 the first of the second.  (Leftmost-first drops the
+    (upload_layout.hpp, charwise: obits / fbits): 65 535 outputs is the last of the first layout, 65 536 the first of the second.  (Leftmost-first drops the
     patterns that can never match, a word with an earlier word as its prefix, so that kind stays a few outputs below the edge.)"""
     pats, vals, text = synth.patterns_charwise_outputs(n_outputs)
     host = _host(text)
@@ -499,7 +499,7 @@ def test_charwise_output_layouts(n_outputs):
 
 
 def test_charwise_output_layout_unfiltered():
-    """2^24 outputs: the walker records carry no child filter (api_upload.hip:130).  The dictionary (16 777 216 patterns, almost all copies of
+    """2^24 outputs: the walker records carry no child filter (upload_layout.hpp, charwise: obits / fbits).  The dictionary (16 777 216 patterns, almost all copies of
     one the text holds once) takes about 15 s to generate and build on the host, so this case runs count and count + checksum of every
     iterator, and the overlapping tuples, only.  Standard and leftmost-longest reach 2^24 outputs; leftmost-first drops the patterns that
     can never match and stays in the 24-bit layout"""

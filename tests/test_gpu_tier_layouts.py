@@ -1,6 +1,6 @@
 """The TIERED engine on the MI355X under every tier layout TierEngine::step has a route for (tests/tier_layouts.py; that each layout
 exists is proved on the CPU by tests/test_tier_layouts_host.py): 16-bit and 32-bit dense rows, tier-B misses and hits, tier-C records,
-the LDS block's offsets as api_upload.hip computes them, and the histogram's LDS bins behind table blocks of other sizes.
+the LDS block's offsets as upload_layout.hpp (tiered) computes them, and the histogram's LDS bins behind table blocks of other sizes.
 
 Expected values come from the CPU oracle, never from the library: tuples are compared exactly (start, end, value, order), counts,
 checksums and per-slot histogram counts exactly.  Every call names Engine.Tiered and is followed by an assertion that TIERED served it,
@@ -39,7 +39,7 @@ def _pad16(x):
 
 
 def _table_bytes(shape, C):
-    """the LDS block as api_upload.hip lays it out: rows, tier B's bitmaps and fail links, the dense states' sums, the byte classes"""
+    """the LDS block as upload_layout.hpp (tiered) lays it out: rows, tier B's bitmaps and fail links, the dense states' sums, the byte classes"""
     return _pad16(shape["NA"] * C * (4 if shape["row32"] else 2)) + 2 * _pad16((shape["NB"] - shape["NA"]) * 4) + _pad16(shape["NA"] * 8) + 256
 
 
