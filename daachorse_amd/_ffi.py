@@ -228,7 +228,9 @@ def last_engine():
 
 
 def last_kernel():
-    """daac_last_kernel: kernel family + launch shape of this thread's most recent count (a diagnostic string)"""
+    """daac_last_kernel: kernel family + launch shape of this thread's most recent count (a diagnostic string).  The first word is the family;
+    gram4, gram, gram2 and gram2w follow it with key=value fields that name the compiled instance and the launch's regions, e.g.
+    `gram K=3 short=1 waves=16 dense=0 rank=lds ppl=16 region=2048 regions=7 slab=1216` (an empty range launches nothing: the family alone)"""
     return lib().daac_last_kernel().decode()
 
 

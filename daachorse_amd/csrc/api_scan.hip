@@ -456,6 +456,21 @@ std::pair<int, int> count_ids(const DeviceTables *t, const CountPlan &cp) {
     }
 }
 
+// what daac_last_kernel() says after a launch of one of the count + checksum GRAM kernels: the family, then the template instance that ran
+// (as launch_gram_scan / launch_gram2_scan / launch_gram2w_scan pick it from these same values) and the launch's regions
+static std::string gram_launch_name(const CountPlan &cp, const DeviceTables *t, const GramArgs &ga, bool want_checksum) {
+    const std::string regions = " region=" + std::to_string(ga.region_bytes) + " regions=" + std::to_string(ga.nregions);
+    const std::string waves = " waves=" + std::to_string(cp.threads / 64), dense = " dense=" + std::to_string(ga.dense ? 1 : 0);
+    if (cp.kernel == CountKernel::gram) {
+        const bool p32 = !t->gram.has_short && cp.threads > 768 && ga.ppl == 32;   // (gram_kernels.hip, launch_rl)
+        return "gram K=" + std::to_string(t->gram.K) + " short=" + std::to_string(t->gram.has_short ? 1 : 0) + waves + dense + " rank=" +
+               (t->gram.rank_in_lds ? "lds" : "l2") + " ppl=" + (p32 ? "32" : "16") + regions + " slab=" + std::to_string(ga.wq_slab);
+    }
+    if (cp.kernel == CountKernel::gram2)
+        return "gram2 K=" + std::to_string(t->gram2.K) + " dir=" + (t->gram2.s16 ? "1" : "2") + dense + waves + regions;
+    return std::string("gram2w exact=") + (want_checksum ? "1" : "0") + regions;
+}
+
 // what daac_last_kernel() says: the kernel family and, for the `.count()` kernel, the launch shape the options gave it
 static std::string count_kernel_name(const CountPlan &cp, const std::string &regions = std::string()) {
     static const char *const family[] = {"gram4", "gram", "gram2", "gram2w", "pfx"};
@@ -605,6 +620,9 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
         }
         // more than ~1 % of the (K+1)-grams are trie prefixes: some lane of the wave hits on nearly every position
         ga.dense = OPT(gram_dense) >= 0 ? OPT(gram_dense) != 0 : cp.n_deep * 100 > cp.C * cp.C * cp.C * (cp.K == 3 ? cp.C : 1);
+        // daac_last_kernel(): the other three GRAM families name the instance and the regions of this launch (a shard's halo launch runs the same one)
+        if (cp.kernel == CountKernel::gram || cp.kernel == CountKernel::gram2 || cp.kernel == CountKernel::gram2w)
+            g_last_kernel = gram_launch_name(cp, t, ga, want_checksum);
         // gram4: tail records from the hit record on pay on text made of dictionary words (+20 %) and cost 3-4 % elsewhere; unless
         // the option decides, every workgroup samples the haystack at its start and runs the variant the text calls for
         const int64_t tail_opt = OPT(gram_tail);

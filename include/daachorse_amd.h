@@ -203,6 +203,10 @@ void daac_free(void *p);
 int daac_last_engine(void);
 /* The kernel family — and, for the `.count()` kernel, the launch shape the options in force gave it ("gram4 ppl=32 dir=0 waves=16 arith=1 filter=1
  * mph=1 regions=23552 claims=11264 tail=auto": regions of the launch, and how many of them its waves claim from the call's counter) — that served the calling thread's last daac_scan_count* call (daac_scan_count_multi: shard 0's, as run by its device's worker).
+ * The count + checksum GRAM kernels name the compiled instance that ran and the launch's regions: "gram K=3 short=1 waves=16 dense=0 rank=lds ppl=16
+ * region=2048 regions=7 slab=1216" (rank: the rank directory in the LDS or read from the L2), "gram2 K=3 dir=1 dense=0 waves=16 region=.. regions=.."
+ * (dir=2: 32-bit directory entries), "gram2w exact=1 region=.. regions=.." (exact=0: `.count()` alone); a call that launches nothing
+ * (an empty range) says the family alone.
  * ABI 6; a diagnostic: the text is not a contract. */
 const char *daac_last_kernel(void);
 

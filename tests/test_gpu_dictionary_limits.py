@@ -310,6 +310,82 @@ def test_full_range_values_wide():
     _all_kinds(pats, vals, host, lazy=False, stepper=False)
 
 
+# ---------------------------------------------------------------------------------------------------------- count = (h32 != 0)
+# The 8-byte hit record of a depth-(K+1) state carries no count: gram_kernels.hip and gram2_kernels.hip take count = (h32 != 0) there, and the
+# table builders decline a K whose depth-(K+1) states break that.  tests/gram_exact.py has (length, value) pairs whose match_hash32 is 0.
+# Which K each table set takes for each case, read once from info() on the device and from the layout on the CPU, with the builder's line:
+#   (gram_available, gram_k, gram2_available, gram2_k)
+ZERO_HASH_TABLES = {
+    # a 2-byte word with h32 = 0 is a short pattern for K = 3: COMBO holds {count 1, sum 0} (gram.cpp:84), gram2's M word counts it in its
+    # two count bits and its H entry adds 0 (gram2.cpp:124): nothing at depth 4 is irregular, both keep K = 3
+    "z_short": (1, 3, 1, 3),
+    # a 4-byte word with h32 = 0 is a depth-4 state with a count of 1 and a sum of 0: K = 3 declined (gram.cpp:66, gram2.cpp:105), both take K = 2
+    "z_k3": (1, 2, 1, 2),
+    # ... and a 3-byte one on top breaks K = 2 as well: no GRAM table set at all (gram.cpp:98 returns false; gram2.cpp likewise), PFX or the walkers serve
+    "z_k2": (0, 0, 0, 0),
+    # zero hashes at depth 7 and 8 are below depth K + 1: the walkers' records carry their own count (gram.cpp:119) and a tail record adds 1
+    # whatever h is (gram_kernels.hip:193): K = 3 stays
+    "z_deep": (1, 3, 1, 3),
+    # one 4-byte word twice: a depth-4 state with count 2, K = 3 declined by both (gram.cpp:66, gram2.cpp:105)
+    "dup_k": (1, 2, 1, 2),
+    # four patterns ending at one 3-gram: v1's COMBO holds any count (K = 3); gram2's M word has two count bits (gram2.cpp:124: at most 3) and the
+    # 3-byte word registered twice is an irregular depth-3 state for K = 2: no second table set
+    "four_short": (1, 3, 0, 0),
+}
+
+
+@pytest.fixture(scope="module")
+def zero_hash_cases():
+    import gram_exact as ge
+    out = {}
+    for name, (pats, vals, special) in ge.zero_hash_cases().items():
+        out[name] = (pats, vals, special, ge.special_text(pats, special))
+    return out
+
+
+@pytest.mark.parametrize("case", list(ENGINE_CASES))
+@pytest.mark.parametrize("name", list(ZERO_HASH_TABLES))
+def test_patterns_that_break_count_is_h_nonzero(zero_hash_cases, name, case):
+    """k3s with a pattern whose hash is 0 (or two patterns at one state) where the hit record would have to carry a count, through every engine:
+    every entry point gives the oracle's answer, a forced engine may refuse (status 6), AUTO may not; the table sets take the K written
+    down above.  The text has each special word at its start, at its end, ending at offsets 1023 and 2047 and cut one byte short."""
+    pats, vals, special, host = zero_hash_cases[name]
+    opts, engine, kernel = ENGINE_CASES[case]
+    forced = engine != Engine.Auto
+    o, p = _pair(pats, vals, orc.STANDARD, opts=opts)
+    info = p.info()
+    assert (info.gram_available, info.gram_k, info.gram2_available, info.gram2_k) == ZERO_HASH_TABLES[name], (name, p.explain())
+    served = sweep(o, p, host, orc.STANDARD, engine=engine, refuse=forced, cuts=[1023, 1024, 2047, 2048])
+    names = set(served[ScanMode.FindOverlapping])
+    if not forced:
+        assert {"count", "scan_count", "scan", "scan_device24", "scan_device16", "batch", "multi"} <= names, (name, case, names)
+    # the first special word at the very end, the last at the very start
+    dev = torch.from_numpy(host).cuda()
+    first, last = special[0], special[-1]
+    for a, b in ((0, len(host)), (len(first) + 1, len(host)), (0, len(host) - len(last) - 1), (0, len(host) - 1)):
+        want = o.find_overlapping_iter(host[a:b])
+        # (each call on its own: a forced engine that refuses one of them, as the sweep found, must still answer the other)
+        for call, answer in (("scan_count", (len(want), orc.matches_checksum(want))), ("count", len(want))):
+            try:
+                got = getattr(p, call)(ScanMode.FindOverlapping, dev[a:b], engine=engine)
+            except da.DaachorseError as e:
+                assert e.code == 6 and forced and call not in names, (name, case, call, str(e))
+                continue
+            assert got == answer and call in names, (name, case, call, a, b, got, answer)
+    # the forced GRAM kernels ran on the K the builders took, or refused where there is no table set
+    v1_k, v2_k = ZERO_HASH_TABLES[name][1], ZERO_HASH_TABLES[name][3]
+    if case == "gram_v1":
+        assert ("scan_count" in names) == (v1_k != 0), (name, names)
+        if v1_k:
+            p.scan_count(ScanMode.FindOverlapping, dev, engine=engine)
+            assert da.last_kernel().split()[:2] == ["gram", f"K={v1_k}"], da.last_kernel()
+    if case == "gram_v2":
+        assert ("scan_count" in names) == (v2_k != 0), (name, names)
+        if v2_k:
+            p.scan_count(ScanMode.FindOverlapping, dev, engine=engine)
+            assert da.last_kernel().split()[:2] == ["gram2", f"K={v2_k}"], da.last_kernel()
+
+
 # ---------------------------------------------------------------------------------------------------------- lengths
 def _k_of_words():
     """K of the table set the handle builds for the families' words (read from the handle, not assumed)"""

@@ -172,7 +172,7 @@ def test_engine_plan_says_what_will_run():
             p.set_option(k, v)
         info = _counts_run_as_planned(p.upload(), hay)
         if opts == {"gram_version": 2}:   # (a dictionary with the count + checksum tables: `.count()` on gram2_kernels.hip)
-            assert da.last_kernel() == "gram2" and info.plan_kernel[0] == 2
+            assert da.last_kernel().split()[:3] == ["gram2", f"K={info.gram2_k}", "dir=1"] and info.plan_kernel[0] == 2, da.last_kernel()
     for pats in (synth.patterns_cfg3_wide(30000), synth.patterns_binary256(5000), synth.patterns_binary256(5000) + [b""]):
         p, _ = da.DoubleArrayAhoCorasick.deserialize(orc.OraclePma.build(pats).serialize())
         info = _counts_run_as_planned(p.upload(), hay)
