@@ -11,7 +11,7 @@ from .bytewise import (DoubleArrayAhoCorasick, DoubleArrayAhoCorasickBuilder, En
                        MATCH_DTYPE, MATCH16_DTYPE, SLOT_COUNT_DTYPE, scan_count_multi,
                        Split, Splitter, char_classes, split_batch, offsets_compose, bert_char_classes, o200k_char_classes, wordpiece_tables,
                        Norm, Normalizer, bert_normalizer, bert_normalizer_rules, SpecialTokens, splice_special,
-                       Packer, bert_template, roberta_template)
+                       Packer, bert_template, roberta_template, Decoder)
 from .charwise import CharwiseDoubleArrayAhoCorasick, CharwiseDoubleArrayAhoCorasickBuilder
 
 _ffi.lib()  # fail loudly at import time if the extension is missing
@@ -21,4 +21,4 @@ __all__ = ["DoubleArrayAhoCorasick", "DoubleArrayAhoCorasickBuilder", "CharwiseD
            "DaachorseError", "set_option", "last_engine", "last_kernel", "MATCH_DTYPE", "MATCH16_DTYPE", "SLOT_COUNT_DTYPE", "scan_count_multi",
            "Split", "Splitter", "char_classes", "split_batch", "offsets_compose", "bert_char_classes", "o200k_char_classes",
            "wordpiece_tables", "Norm", "Normalizer", "bert_normalizer", "bert_normalizer_rules", "SpecialTokens", "splice_special",
-           "Packer", "bert_template", "roberta_template"]
+           "Packer", "bert_template", "roberta_template", "Decoder"]

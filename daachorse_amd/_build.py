@@ -11,8 +11,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libdaachorse_amd.so")
 
 SOURCES = ["pma.cpp", "repack.cpp", "gram.cpp", "gram2.cpp", "gram4.cpp", "gram2w.cpp", "pfx.cpp", "builder.cpp", "charwise.cpp", "charwise_builder.cpp", "api_upload.hip", "api_scan.hip", "api_select.hip", "api_iter.hip", "api_options.hip", "scan_kernels.hip",
            "gram_kernels.hip", "gram2_kernels.hip", "gram4_kernels.hip", "pfx_kernels.hip", "emit3_kernels.hip", "find3_kernels.hip", "left3_kernels.hip", "gram2w_kernels.hip", "restart_kernels.hip", "charwise_kernels.hip", "synth.hip",
-           "api_batch.hip", "batch_kernels.hip", "batch_hist_kernels.hip", "api_hist.hip", "hist_kernels.hip", "api_replace.hip", "replace_kernels.hip", "api_tokenize.hip", "tokenize_kernels.hip", "api_unigram.hip", "unigram_kernels.hip", "api_bpe.hip", "bpe_kernels.hip", "api_split.hip", "split_kernels.hip", "api_wordpiece.hip", "wordpiece_kernels.hip", "api_normalize.hip", "normalize_kernels.hip", "api_cut.hip", "cut_kernels.hip", "api_tokens.hip", "api_pack.hip", "pack_kernels.hip"]
-HEADERS = ["api_internal.hpp", "pma.hpp", "repack.hpp", "gram.hpp", "gram2.hpp", "gram4.hpp", "gram4_claims.hpp", "gram4_filter.hpp", "gram4_index.hpp", "gram4_mph.hpp", "gram2w.hpp", "pfx.hpp", "charwise.hpp", "build_common.hpp", "device_tables.hpp", "upload_layout.hpp", "chain_scan.hpp", "scan_engines.hpp", "restart_tables.hpp", "char_tables.hpp", "batch.hpp", "hist.hpp", "replace.hpp", "tokenize.hpp", "unigram.hpp", "bpe.hpp", "split.hpp", "wordpiece.hpp", "normalize.hpp", "cut.hpp", "pack.hpp",
+           "api_batch.hip", "batch_kernels.hip", "batch_hist_kernels.hip", "api_hist.hip", "hist_kernels.hip", "api_replace.hip", "replace_kernels.hip", "api_tokenize.hip", "tokenize_kernels.hip", "api_unigram.hip", "unigram_kernels.hip", "api_bpe.hip", "bpe_kernels.hip", "api_split.hip", "split_kernels.hip", "api_wordpiece.hip", "wordpiece_kernels.hip", "api_normalize.hip", "normalize_kernels.hip", "api_cut.hip", "cut_kernels.hip", "api_tokens.hip", "api_pack.hip", "pack_kernels.hip", "api_decode.hip", "decode_kernels.hip"]
+HEADERS = ["api_internal.hpp", "pma.hpp", "repack.hpp", "gram.hpp", "gram2.hpp", "gram4.hpp", "gram4_claims.hpp", "gram4_filter.hpp", "gram4_index.hpp", "gram4_mph.hpp", "gram2w.hpp", "pfx.hpp", "charwise.hpp", "build_common.hpp", "device_tables.hpp", "upload_layout.hpp", "chain_scan.hpp", "scan_engines.hpp", "restart_tables.hpp", "char_tables.hpp", "batch.hpp", "hist.hpp", "replace.hpp", "tokenize.hpp", "unigram.hpp", "bpe.hpp", "split.hpp", "wordpiece.hpp", "normalize.hpp", "cut.hpp", "pack.hpp", "decode.hpp",
            os.path.join("..", "..", "include", "daachorse_amd.h"),
            os.path.join("..", "..", "include", "daac_synth.h")]
 

@@ -192,6 +192,12 @@ def lib():
     L.daac_tokens_pack.argtypes = [P(PackParams), vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, sz, vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp),
                                    P(C.c_uint64), P(C.c_uint64)]
     L.daac_tokens_pack.restype = C.c_int
+    L.daac_decoder_create.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, P(vp)]
+    L.daac_decoder_create.restype = C.c_int
+    L.daac_decoder_free.argtypes = [vp]
+    L.daac_decoder_free.restype = None
+    L.daac_tokens_decode.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint64, sz, C.c_uint64, C.c_int, C.c_int, vp, P(vp), P(vp), P(vp), P(C.c_uint64)]
+    L.daac_tokens_decode.restype = C.c_int
     L.daac_device_free.argtypes = [vp]
     L.daac_device_to_host.argtypes = [vp, vp, sz]
     L.daac_device_to_host.restype = C.c_int

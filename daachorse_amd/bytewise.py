@@ -1537,6 +1537,265 @@ def _pack_docs(pack, out, stream, device):
     return Packer._result(res, device)
 
 
+# ---- token ids back to text (daac_decoder_create / daac_tokens_decode): `tokenizers`' decoders as one rule over a table of images, for a
+# token result or a plane of ids that is already in device memory.
+DECODE_SPECIAL, DECODE_ABSENT = 1, 2   # DAAC_DECODE_SPECIAL, DAAC_DECODE_ABSENT
+_WORDPIECE_CLEANUP = ((b" .", b"."), (b" ?", b"?"), (b" !", b"!"), (b" ,", b","), (b" ' ", b"'"), (b" n't", b"n't"), (b" 'm", b"'m"), (b" do not", b" don't"),
+                      (b" 's", b"'s"), (b" 've", b"'ve"), (b" 're", b"'re"))   # `tokenizers`' cleanup, in its order
+
+
+class Decoder:
+    """daac_decoder: a table of images over the ids 0 .. n_ids - 1.  `rest` is a sequence indexed by id, or a {id: image} mapping, of
+    str / bytes images (None, or an id the mapping leaves out: the id has no entry); `first` likewise, the image a token takes as the
+    first KEPT token of its document (None: `rest` throughout; an id it leaves out takes its rest image).  `special`: the ids that
+    skip_special_tokens leaves out, or a SpecialTokens, whose ids are flagged and whose images are the specials' own text.  A
+    document's text is first[k_0] + rest[k_1] + rest[k_2] + ... over its kept tokens: bytes, never validated or replaced as UTF-8.
+    byte_level(), wordpiece() and metaspace() build the tables of `tokenizers`' decoders."""
+
+    def __init__(self, rest, first=None, special=()):
+        self._h = None
+        r, f = self._images(rest, "rest"), ({} if first is None else self._images(first, "first"))
+        ids, texts = self._special(special)
+        for i, t in texts.items():
+            r[i] = t
+            f.pop(i, None)
+        if set(f) - set(r):
+            raise DaachorseError(1, f"first has an image for id {min(set(f) - set(r))}, which has no rest image")
+        n = max(list(r) + list(ids), default=-1) + 1
+        pieces, flags, pool, seen = np.zeros((n, 4), dtype=np.uint32), np.full(n, DECODE_ABSENT, dtype=np.uint8), bytearray(), {}
+
+        def place(img):
+            at = seen.get(img)
+            if at is None:
+                at = seen[img] = len(pool)
+                pool.extend(img)
+            return at, len(img)
+
+        for i, img in r.items():
+            pieces[i, 0:2] = place(img)
+            pieces[i, 2:4] = place(f.get(i, img))
+            flags[i] = 0
+        for i in ids:
+            flags[i] |= DECODE_SPECIAL
+        if len(pool) >= 1 << 32:
+            raise DaachorseError(1, f"the images take {len(pool)} bytes: the pool is below 4 GiB")
+        self.n_ids, self.pool_bytes = n, len(pool)
+        self.rest, self.first, self.special = r, f, frozenset(ids)
+        pool_arr = np.frombuffer(bytes(pool) or b"\0", dtype=np.uint8)
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().daac_decoder_create(pool_arr.ctypes.data, len(pool), pieces.ctypes.data if n else None, flags.ctypes.data if n else None, n,
+                                                  C.byref(h)))
+        self._h = h.value
+
+    @staticmethod
+    def _images(x, what):
+        items = x.items() if hasattr(x, "items") else enumerate(x)
+        out = {}
+        for i, img in items:
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < SEGMENT_TEXT:
+                raise DaachorseError(1, f"{what}: the id {i!r} is not in 0 .. 0xFFFFFFFE")
+            if img is not None:
+                out[int(i)] = _as_bytes(img)
+        return out
+
+    @staticmethod
+    def _special(special):
+        """-> (the flagged ids, {id: text} of a SpecialTokens)"""
+        if isinstance(special, SpecialTokens):
+            if special.tokens is None:
+                raise DaachorseError(1, "special: a SpecialTokens made from an automaton has no texts; give the ids")
+            return sorted(special.tokens.values()), {i: t for t, i in special.tokens.items()}
+        ids = []
+        for i in special:
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < SEGMENT_TEXT:
+                raise DaachorseError(1, f"special: ids in 0 .. 0xFFFFFFFE or a SpecialTokens, not {i!r}")
+            ids.append(int(i))
+        return sorted(set(ids)), {}
+
+    @staticmethod
+    def _by_id(pieces, what):
+        """a vocabulary as {piece: id}, or a sequence of pieces indexed by id -> {id: the piece's bytes}"""
+        out = {}
+        for k, i in (pieces.items() if hasattr(pieces, "items") else ((p, i) for i, p in enumerate(pieces))):
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < SEGMENT_TEXT:
+                raise DaachorseError(1, f"{what}: the id of {k!r} is not in 0 .. 0xFFFFFFFE")
+            if int(i) in out:
+                raise DaachorseError(1, f"{what}: the id {i} comes twice")
+            out[int(i)] = _as_bytes(k)
+        return out
+
+    @classmethod
+    def _build(cls, table, special, rest_of, first_of):
+        ids, texts = cls._special(special)
+        table.update(texts)   # a special goes through the decoder as any token does: `tokenizers` prints it that way
+        return cls({i: rest_of(p) for i, p in table.items()}, {i: first_of(p) for i, p in table.items()}, ids)
+
+    @classmethod
+    def byte_level(cls, pieces, gap_id=None, special=()):
+        """Byte-level BPE and tiktoken-style rank files: first = rest = the piece's raw bytes, the patterns of the automaton.  `pieces`
+        is {piece: id} or a sequence indexed by id; with `gap_id` the ids gap_id + b are the single byte b (Gap.Bytes)."""
+        table = cls._by_id(pieces, "pieces")
+        if gap_id is not None:
+            if isinstance(gap_id, bool) or not 0 <= int(gap_id) <= SEGMENT_TEXT - 256:
+                raise DaachorseError(1, "gap_id + 255 must be in 0 .. 0xFFFFFFFE")
+            for b in range(256):
+                table.setdefault(int(gap_id) + b, bytes([b]))
+        return cls._build(table, special, lambda p: p, lambda p: p)
+
+    @classmethod
+    def wordpiece(cls, vocab, prefix="##", cleanup=True, special=()):
+        """`tokenizers`' decoders.WordPiece: rest is the piece without its prefix, or " " + piece; first is the piece as written (a
+        leading prefix stays); with cleanup the eleven replacements are applied to each image."""
+        pre = _as_bytes(prefix)
+
+        def clean(img):
+            if cleanup:
+                for old, new in _WORDPIECE_CLEANUP:
+                    img = img.replace(old, new)
+            return img
+
+        return cls._build(cls._by_id(vocab, "vocab"), special, lambda p: clean(p[len(pre):] if pre and p.startswith(pre) else b" " + p), clean)
+
+    @classmethod
+    def metaspace(cls, pieces, replacement="▁", prepend_scheme="always", byte_fallback=False, special=(), first=None):
+        """Metaspace / SentencePiece: every `replacement` in the piece becomes a space; with byte_fallback a piece <0xHH> is the byte
+        HH.  Under prepend_scheme "always" or "first" the first image differs, in one of two ways: first="strip_one" takes one leading
+        space off (Llama-2's Sequence([Replace, ByteFallback, Fuse, Strip(" ", 1, 0)]); the default with byte_fallback), and
+        first="drop_all" leaves out every `replacement` of the piece (what `tokenizers`' decoders.Metaspace does to token 0; the
+        default without byte_fallback).  The two agree on every piece whose only `replacement` is a leading one."""
+        rep = _as_bytes(replacement)
+        if prepend_scheme not in ("always", "first", "never") or first not in (None, "strip_one", "drop_all") or not rep:
+            raise DaachorseError(1, 'prepend_scheme is "always", "first" or "never", first "strip_one", "drop_all" or None, and replacement is not empty')
+        how = first or ("strip_one" if byte_fallback else "drop_all")
+        hexd = b"0123456789ABCDEFabcdef"
+
+        def byte_of(p):
+            if byte_fallback and len(p) == 6 and p[:3] == b"<0x" and p[5:] == b">" and p[3] in hexd and p[4] in hexd:
+                return bytes([int(p[3:5], 16)])
+            return None
+
+        def rest_of(p):
+            b = byte_of(p)
+            return b if b is not None else p.replace(rep, b" ")
+
+        def first_of(p):
+            if prepend_scheme == "never":
+                return rest_of(p)
+            if how == "drop_all" and byte_of(p) is None:
+                return p.replace(rep, b"")
+            img = rest_of(p)
+            return img[1:] if img.startswith(b" ") else img
+
+        return cls._build(cls._by_id(pieces, "pieces"), special, rest_of, first_of)
+
+    @staticmethod
+    def _upload(a, keep):
+        import torch
+        t = torch.from_numpy(a.view(np.int32 if a.dtype.itemsize == 4 else np.int64).copy()).cuda()
+        keep.append(t)
+        return t.data_ptr() if t.numel() else None
+
+    @classmethod
+    def _tokens(cls, tokens, keep):
+        """-> (ids address, element width, offsets address or None, tokens, documents, row length)"""
+        if isinstance(tokens, (tuple, list)):
+            if len(tokens) not in (2, 3):
+                raise DaachorseError(1, "a CSR token result is (ids, offsets) or (ids, spans, offsets)")
+            ids, off = tokens[0], tokens[-1]
+            host_ids, host_off = isinstance(ids, (np.ndarray, list, tuple)), isinstance(off, (np.ndarray, list, tuple))
+            if host_ids:   # (both are looked at before either is uploaded)
+                a = np.asarray(ids)
+                if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xFFFFFFFF)):
+                    raise DaachorseError(1, "ids of a CSR token result are one-dimensional integers in 0 .. 0xFFFFFFFF")
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+            if host_off:
+                o = np.asarray(off)
+                if o.ndim != 1 or o.size < 1 or o.dtype.kind not in "iu" or (o.dtype.kind == "i" and o.min() < 0):
+                    raise DaachorseError(1, "offsets hold n + 1 non-negative integers")
+                o = np.ascontiguousarray(o, dtype=np.uint64)
+            p_ids, n_tok = (cls._upload(a, keep), a.size) if host_ids else _device_ptr(ids, 4, "ids")
+            p_off, n_off = (cls._upload(o, keep), o.size) if host_off else _device_ptr(off, 8, "offsets")
+            if n_off < 1 or not p_off:
+                raise DaachorseError(1, "offsets hold n + 1 entries and have not been freed")
+            return (p_ids if n_tok else None), 4, p_off, n_tok, n_off - 1, 0
+        x = tokens
+        if isinstance(x, DeviceMatches):
+            shape = getattr(x, "shape", None)
+            if shape is None or len(shape) != 2 or x.dtype.base.kind not in "iu" or x.dtype.base.itemsize not in (4, 8):
+                raise DaachorseError(1, "a DeviceMatches plane has .shape == (n, L) and int32 / uint32 / int64 elements")
+            if shape[0] * shape[1] and not x.ptr:
+                raise DaachorseError(1, "the plane has been freed")
+            return x.ptr, x.dtype.base.itemsize, None, shape[0] * shape[1], shape[0], shape[1]
+        if hasattr(x, "data_ptr") and hasattr(x, "is_cuda"):
+            if not x.is_cuda or x.dim() != 2 or not x.is_contiguous() or x.dtype.is_floating_point or x.dtype.itemsize not in (4, 8):
+                raise DaachorseError(1, "a plane of ids is a contiguous two-dimensional CUDA tensor of int32 / uint32 / int64")
+            return (x.data_ptr() if x.numel() else None), x.dtype.itemsize, None, x.numel(), x.shape[0], x.shape[1]
+        if isinstance(x, np.ndarray):
+            if x.ndim != 2 or x.dtype not in (np.dtype(np.int32), np.dtype(np.uint32), np.dtype(np.int64)):
+                raise DaachorseError(1, "a plane of ids is a two-dimensional array of int32 / uint32 / int64")
+            a = np.ascontiguousarray(x)
+            return cls._upload(a.reshape(-1), keep), a.dtype.itemsize, None, a.size, a.shape[0], a.shape[1]
+        raise DaachorseError(1, "tokens is (ids, offsets), (ids, spans, offsets) or one two-dimensional plane of ids")
+
+    def _run(self, tokens, skip_special_tokens, unknown, token_starts, stream):
+        """-> [text (uint8), out_offsets] or [text, out_offsets, token_starts], in device memory"""
+        if not self._h:
+            raise DaachorseError(1, "the decoder has been freed")
+        if unknown not in ("error", "skip"):
+            raise DaachorseError(1, 'unknown is "error" or "skip"')
+        keep = []
+        p_ids, width, p_off, n_tok, n, L = self._tokens(tokens, keep)
+        out, oo, ts, nb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _ffi.check(_ffi.lib().daac_tokens_decode(self._h, p_ids, width, p_off, n_tok, n, L, int(bool(skip_special_tokens)), int(unknown == "skip"), stream,
+                                                 C.byref(out), C.byref(oo), C.byref(ts) if token_starts else None, C.byref(nb)))
+        del keep
+        res = [DeviceMatches(out.value, nb.value, np.dtype(np.uint8)), DeviceOffsets(oo.value, n + 1)]
+        if token_starts:
+            res.append(DeviceOffsets(ts.value, n_tok + 1 if ts.value else 0))
+        return res
+
+    def decode_batch(self, tokens, skip_special_tokens=True, unknown="error", token_starts=False, stream=None, device=False):
+        """`tokens` is (ids, offsets) or (ids, spans, offsets) as every token call returns them (DeviceMatches / DeviceOffsets,
+        contiguous CUDA tensors, or numpy arrays, which are uploaded; the spans are not read), or one [n, L] plane of ids: a
+        DeviceMatches with .shape == (n, L) as Packer leaves it, a contiguous CUDA tensor or a numpy array of int32 / uint32 / int64,
+        where an int64 outside 0 .. 2^32 - 1 (-100) is an id without an entry.  unknown="error" refuses the batch at its lowest such
+        token, "skip" leaves them out as `tokenizers` does.  -> a list of bytes, one per document; with token_starts=True (that list,
+        np.uint64[T + 1]: where each token's image begins in the concatenated text).  device=True: (DeviceMatches uint8,
+        DeviceOffsets), a batch again that goes into tokenize_*_docs or normalize_batch, and the starts as DeviceOffsets"""
+        res = self._run(tokens, skip_special_tokens, unknown, token_starts, stream)
+        if device:
+            return tuple(res)
+        try:
+            text, off = res[0].to_numpy().tobytes(), res[1].to_numpy()
+            docs = [text[int(off[d]):int(off[d + 1])] for d in range(len(off) - 1)]
+            return (docs, res[2].to_numpy()) if token_starts else docs
+        finally:
+            for r in res:
+                r.free()
+
+    def decode(self, ids, skip_special_tokens=True, unknown="error", stream=None):
+        """one document's ids (a sequence of integers, or a one-dimensional array or CUDA tensor of 4-byte ids) -> bytes"""
+        if hasattr(ids, "data_ptr"):
+            import torch
+            off = torch.tensor([0, ids.numel()], dtype=torch.int64, device=ids.device)
+        else:
+            ids = np.asarray(ids if isinstance(ids, np.ndarray) else list(ids))
+            ids = ids.astype(np.uint32) if ids.size == 0 else ids   # (an empty list has no integer dtype of its own)
+            off = np.array([0, ids.size], dtype=np.uint64)
+        return self.decode_batch((ids, off), skip_special_tokens=skip_special_tokens, unknown=unknown, stream=stream)[0]
+
+    def free(self):
+        if self._h:
+            _ffi.lib().daac_decoder_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Norm(enum.IntEnum):
     """daac_norm_kind: what a Normalizer's rule does to the code points of its range"""
     Delete = 1     # the code point is removed

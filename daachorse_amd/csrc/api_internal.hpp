@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (include/daachorse_amd.h; api_upload.hip, api_scan.hip, api_select.hip, api_iter.hip,
 // api_options.hip, api_batch.hip, api_tokens.hip, api_hist.hip, api_replace.hip, api_cut.hip, api_split.hip, api_normalize.hip,
-// api_tokenize.hip, api_unigram.hip, api_bpe.hip, api_wordpiece.hip, api_pack.hip): the options, the handle, its device tables, the
+// api_tokenize.hip, api_unigram.hip, api_bpe.hip, api_wordpiece.hip, api_pack.hip, api_decode.hip): the options, the handle, its device tables, the
 // call-scoped buffers and the drivers one unit calls in another.  Internal: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -62,7 +62,9 @@ extern "C" {
  *   (6, likewise: daac_cut_batch / daac_tokens_splice — a batch cut into segments around the special tokens written into its text,
  *      and a tokenizer's result over the segments put back together per document, on the device.)
  *   (6, likewise: daac_tokens_pack and daac_pack_params — a token result wrapped in a template, truncated and padded into the planes a
- *      model reads, on the device.) */
+ *      model reads, on the device.)
+ *   (6, likewise: daac_decoder_create / daac_decoder_free / daac_tokens_decode — token ids back to text, from a CSR token result or a
+ *      dense plane of ids, on the device.) */
 #define DAAC_ABI_VERSION 6
 uint32_t daac_abi_version(void);
 
@@ -917,6 +919,67 @@ daac_status daac_tokens_pack(const daac_pack_params *params, const uint32_t *dev
                              uint64_t b_tokens, size_t n, void *stream, void **dev_input_ids, void **dev_token_type_ids,
                              void **dev_attention_mask, void **dev_special_tokens_mask, uint64_t **dev_offsets, uint64_t **dev_row_offsets,
                              uint64_t *row_length, uint64_t *n_slots);
+
+/* ---- token ids back to text -------------------------------------------------------------------------------------------------------------
+ * What `tokenizers` calls the decoder, and the other direction of every token call above.
+ * A decoder is a table over the ids 0 .. n_ids - 1.  Each id has an image rest (any bytes, possibly none), an image first, used when the
+ *   token is the first KEPT token of its document, and flags: DAAC_DECODE_SPECIAL, and DAAC_DECODE_ABSENT for an id that has no entry
+ *   (its images are not read).  Every id from n_ids on has no entry either.
+ * Definition.  A document's tokens t_0 .. t_{m-1} decode as follows.  A token is kept unless skip_special is set and its id is special,
+ *   or its id has no entry and unknown_skip is set (without unknown_skip such a token is an error).  The document's text is
+ *   first[k_0] + rest[k_1] + rest[k_2] + ... over the kept tokens in order.  The result is bytes: nothing is validated or replaced as
+ *   UTF-8.  This one rule covers `tokenizers`' ByteLevel, WordPiece (cleanup included: it is applied per token) and Metaspace /
+ *   ByteFallback decoders, each of which is a function of the token and of whether it is the first after the specials are filtered; the
+ *   Python package's Decoder.byte_level / .wordpiece / .metaspace build their tables.
+ * daac_decoder_create copies the table: `pool` (pool_bytes, below 4 GiB) holds the images' bytes and pieces[id] = {off, len, first_off,
+ *   first_len} says where rest and first lie in it; flags[id] is a byte.  Status 1: a NULL out, a NULL pool, pieces or flags with
+ *   elements to read, a pool of 4 GiB or more, more than 2^32 ids, a flag bit other than the two, an image that leaves the pool.  The
+ *   table goes to a device the first time a call runs there; daac_decoder_free releases it everywhere.
+ * daac_tokens_decode.  The tokens are in device memory, in one of two forms.  CSR (dev_offsets != NULL): dev_ids holds n_tokens u32
+ *   (id_width 4) and dev_offsets n + 1 u64 token offsets, as every token call leaves them; tokens in front of dev_offsets[0] or behind
+ *   dev_offsets[n] belong to no document and are not looked at.  Dense (dev_offsets == NULL): dev_ids is an [n, row_length] plane of
+ *   id_width-byte elements (4: int32 / uint32, 8: int64), daac_tokens_pack's planes or a model's output; row d is tokens d * row_length
+ *   .. d * row_length + row_length - 1, n_tokens is not read, and an 8-byte element outside [0, 2^32), -100 for instance, is an id
+ *   without an entry.  Padding is just a special id.
+ *   Result, in device memory, released with daac_device_free: *dev_out, *out_bytes bytes of text (never NULL when n > 0: a text of no
+ *   byte is a granule nobody reads); *dev_out_offsets, n + 1 u64 from 0, document d's text is [out_offsets[d], out_offsets[d + 1]) — a
+ *   batch again, as every batch call takes it; and, where dev_token_starts is not NULL, *dev_token_starts: n_tokens + 1 (dense: n *
+ *   row_length + 1) u64, the position in the text at which each token's image begins, the total as the closing entry (a token that is
+ *   not kept has the position of the next one).  n = 0: one 0 in out_offsets and no other buffer.  The call is ordered on `stream` and
+ *   returns after it has finished.
+ *   Deliberate differences from `tokenizers`: the result is raw bytes, as tiktoken's decode_bytes (`tokenizers` turns ill-formed UTF-8
+ *   into U+FFFD); an id without an entry is an error unless unknown_skip is set (`tokenizers` drops it silently: unknown_skip);
+ *   `transformers`' clean_up_tokenization_spaces over the joined string, and incremental decoding that keeps state between calls, are out
+ *   of scope.
+ *   Decided before a device is touched, in this order: status 1 for a NULL dec, dev_out, dev_out_offsets or out_bytes, or a NULL
+ *   dev_ids with tokens to read; an id_width other than 4 or 8, or 8 with dev_offsets; neither dev_offsets nor a row_length while n > 0;
+ *   then status 2 where out_offsets (8 bytes a document), a dense plane's token count (8 bytes a token of scratch) or token_starts (8
+ *   bytes a token) exceed the process-wide option max_result_bytes.  A call refused so far leaves its out-pointers as given.
+ *   After the sizing pass, one read-back: the first document whose offsets decrease or leave [0, n_tokens] answers 1 ("document <d>:
+ *   ..."), then the lowest token whose id has no entry ("document <d>, token <i>: ...", i the flat index), then a text above
+ *   max_result_bytes answers 2 before it is allocated; nothing is handed over and every out-pointer is NULL.
+ *   daac_last_kernel() says "decode docs=.. tokens=.. kept=.. bytes=..".
+ *   Method: one lane per token writes the length of its rest image (0 if it is not kept) and folds the lowest token without an entry
+ *   (a max over the complement) and the kept tokens, a wave reduction and one atomic per wave on scratch; one lane per document checks
+ *   its offsets, walks to its first kept token and overrides that token's length with its first image's (a document of nothing but
+ *   skipped tokens costs its lane one read per token); an exclusive sum gives every token's start; the copy is output-parallel: a
+ *   workgroup owns 4 KiB of text, a lane 16 bytes and one aligned 16-byte store, the tile's token starts are staged in LDS (up to 4096
+ *   of them; a tile of more, which takes empty images, searches them in HBM), and a lane finds the token of its first byte as the largest i with start[i] <= q,
+ *   which steps over empty images, and gathers its bytes from the pool.  Positions are 64-bit, no pass uses atomics on the output.
+ *   Scratch: 9 bytes a token (1 with token_starts, which are the starts themselves) and 8 bytes per 4 KiB of text. */
+#define DAAC_DECODE_SPECIAL 1u
+#define DAAC_DECODE_ABSENT 2u
+typedef struct {
+    uint32_t off, len;               /* rest = pool[off, off + len) */
+    uint32_t first_off, first_len;   /* first = pool[first_off, first_off + first_len) */
+} daac_decode_piece;
+typedef struct daac_decoder daac_decoder;
+daac_status daac_decoder_create(const uint8_t *pool, uint64_t pool_bytes, const daac_decode_piece *pieces, const uint8_t *flags, uint64_t n_ids,
+                                daac_decoder **out);
+void daac_decoder_free(daac_decoder *dec);
+daac_status daac_tokens_decode(daac_decoder *dec, const void *dev_ids, uint32_t id_width, const uint64_t *dev_offsets, uint64_t n_tokens, size_t n,
+                               uint64_t row_length, int skip_special, int unknown_skip, void *stream, uint8_t **dev_out, uint64_t **dev_out_offsets,
+                               uint64_t **dev_token_starts, uint64_t *out_bytes);
 
 /* The same over the tail of a haystack: counts the matches with end in (begin, len] — what one
  * shard of a haystack split across devices contributes.  Bytes before begin - Lmax are never read (they need

@@ -519,4 +519,45 @@ inline PackedPlanes tokens_pack(const daac_pack_params &params, const uint32_t *
     return r;
 }
 
+// daac_decoder: token ids back to text (the header has the definition).  The table is given as it is uploaded: the images' bytes in one
+// pool, per id where its rest and first image lie, and a flag byte.  The text stays on the device and is the caller's, released with
+// daac_device_free.
+struct DecodedText {
+    uint8_t *text = nullptr;
+    uint64_t *offsets = nullptr, *token_starts = nullptr;
+    uint64_t bytes = 0;
+};
+class Decoder {
+public:
+    Decoder(const std::string &pool, const std::vector<daac_decode_piece> &pieces, const std::vector<uint8_t> &flags) {
+        if (pieces.size() != flags.size()) throw PanicError("Decoder: one flag byte per piece");
+        const daac_status st = daac_decoder_create(reinterpret_cast<const uint8_t *>(pool.data()), pool.size(), pieces.data(), flags.data(), pieces.size(), &h_);
+        if (st != DAAC_OK) throw PanicError(std::string("decoder_create failed: ") + daac_last_error());
+    }
+    ~Decoder() { daac_decoder_free(h_); }
+    Decoder(const Decoder &) = delete;
+    Decoder &operator=(const Decoder &) = delete;
+    // a CSR token result in device memory: n_tokens u32 ids and n + 1 u64 token offsets
+    DecodedText decode(const uint32_t *dev_ids, const uint64_t *dev_offsets, uint64_t n_tokens, size_t n, bool skip_special = true, bool unknown_skip = false,
+                       bool token_starts = false, void *stream = nullptr) const {
+        return run(dev_ids, 4, dev_offsets, n_tokens, n, 0, skip_special, unknown_skip, token_starts, stream);
+    }
+    // an [n, row_length] plane of id_width-byte ids (4 or 8) in device memory
+    DecodedText decode_plane(const void *dev_ids, uint32_t id_width, size_t n, uint64_t row_length, bool skip_special = true, bool unknown_skip = false,
+                             bool token_starts = false, void *stream = nullptr) const {
+        return run(dev_ids, id_width, nullptr, 0, n, row_length, skip_special, unknown_skip, token_starts, stream);
+    }
+
+private:
+    DecodedText run(const void *dev_ids, uint32_t id_width, const uint64_t *dev_offsets, uint64_t n_tokens, size_t n, uint64_t row_length, bool skip_special,
+                    bool unknown_skip, bool token_starts, void *stream) const {
+        DecodedText r;
+        const daac_status st = daac_tokens_decode(h_, dev_ids, id_width, dev_offsets, n_tokens, n, row_length, skip_special, unknown_skip, stream, &r.text, &r.offsets,
+                                                  token_starts ? &r.token_starts : nullptr, &r.bytes);
+        if (st != DAAC_OK) throw PanicError(std::string("tokens_decode failed: ") + daac_last_error());
+        return r;
+    }
+    daac_decoder *h_ = nullptr;
+};
+
 }  // namespace daachorse

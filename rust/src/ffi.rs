@@ -78,6 +78,19 @@ pub struct daac_pack_params {
     pub pad_length: u64,
     pub pad_multiple: u64, //  1: none
 }
+/// where an id's images lie in a decoder's pool (include/daachorse_amd.h: daac_decode_piece)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct daac_decode_piece {
+    pub off: u32,
+    pub len: u32,
+    pub first_off: u32,
+    pub first_len: u32,
+}
+#[repr(C)]
+pub struct daac_decoder {
+    _p: [u8; 0],
+}
 #[repr(C)]
 pub struct daac_pma {
     _p: [u8; 0],
@@ -175,6 +188,15 @@ extern "C" {
                             dev_input_ids: *mut *mut c_void, dev_token_type_ids: *mut *mut c_void, dev_attention_mask: *mut *mut c_void,
                             dev_special_tokens_mask: *mut *mut c_void, dev_offsets: *mut *mut u64, dev_row_offsets: *mut *mut u64,
                             row_length: *mut u64, n_slots: *mut u64) -> i32;
+    /// a decoder's table: the images' bytes in `pool` (below 4 GiB), per id where its rest and first image lie and a flag byte
+    /// (1 special, 2 no entry); copied, uploaded to a device on first use
+    pub fn daac_decoder_create(pool: *const u8, pool_bytes: u64, pieces: *const daac_decode_piece, flags: *const u8, n_ids: u64, out: *mut *mut daac_decoder) -> i32;
+    pub fn daac_decoder_free(dec: *mut daac_decoder);
+    /// token ids back to text: a CSR token result (u32 ids, n + 1 offsets; id_width 4) or, with dev_offsets null, an [n, row_length] plane
+    /// of id_width-byte elements -> the text, n + 1 offsets into it and, if wanted, every token's start in it, in device memory
+    pub fn daac_tokens_decode(dec: *mut daac_decoder, dev_ids: *const c_void, id_width: u32, dev_offsets: *const u64, n_tokens: u64, n: usize, row_length: u64,
+                              skip_special: i32, unknown_skip: i32, stream: *mut c_void, dev_out: *mut *mut u8, dev_out_offsets: *mut *mut u64,
+                              dev_token_starts: *mut *mut u64, out_bytes: *mut u64) -> i32;
     pub fn daac_device_free(p: *mut c_void);
     /// an option for one handle (overrides the process-wide daac_set_option value; unset != 0 removes the override)
     pub fn daac_pma_set_option(pma: *mut daac_pma, name: *const c_char, value: i64, unset: i32) -> i32;
