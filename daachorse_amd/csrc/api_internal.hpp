@@ -82,7 +82,9 @@ const char *last_error_cstr();
     X(batch_hist_wave_max, 2048, 0)      /* batch histograms: most records of a document that one wave sorts in LDS (at most 4096) */            \
     X(batch_hist_sort_max, 16384, 0)     /* ... and that one workgroup sorts (at most 32768: what 160 KB hold); above: dense counters in HBM;    \
                                             both from tools/time_batch_hist.py's sweep (profiles/r12_batch_hist_time.json) */ \
-    X(bpe_doc_max, 4096, 0)              /* tokenize_bpe: longest document it merges (1 .. 65536); a longer one answers 6 */
+    X(bpe_doc_max, 4096, 0)              /* tokenize_bpe: longest document it merges (1 .. 65536); a longer one answers 6 */                    \
+    X(debug_fill, -1, 0)                 /* tests: the byte (0 .. 255) every scratch, staging and result buffer is filled with when it is handed \
+                                            out, in front of the call's own clears and copies (-1 = off: contents undefined, as always) */
 
 enum OptionId : int {
 #define X(NAME, DEF, UP) OPT_##NAME,
@@ -178,9 +180,19 @@ inline void dbg_mark(const char *what) {
     fprintf(stderr, "[mark] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - last).count());
     last = now;
 }
+// Option debug_fill (process-wide: it describes the allocators, not a handle): every byte that dev_malloc, Scratch::alloc and the direct
+// hipMallocs of staging and scratch hand out is first set to that byte, on the call's stream, in front of the call's own clears and copies —
+// what none of them promises otherwise (the pool returns a freed block as the last call left it, the workspace lives from call to call,
+// fresh device memory is zero only by habit).  Off (-1): one relaxed load.  DESIGN.md, "What a call may assume of its scratch".
+inline hipError_t debug_fill(void *p, size_t bytes, hipStream_t s) {
+    const int64_t v = g_opt.v[OPT_debug_fill].load(std::memory_order_relaxed);
+    if (v < 0 || !p || bytes == 0) return hipSuccess;
+    return hipMemsetAsync(p, static_cast<int>(v & 0xff), bytes, s);
+}
 inline hipError_t dev_malloc(void **p, size_t bytes, hipStream_t s) {
     if (bytes == 0) bytes = 16;
-    return pool_mode_of_current_device() == 1 ? hipMallocAsync(p, bytes, s) : hipMalloc(p, bytes);
+    const hipError_t e = pool_mode_of_current_device() == 1 ? hipMallocAsync(p, bytes, s) : hipMalloc(p, bytes);
+    return e == hipSuccess ? debug_fill(*p, bytes, s) : e;
 }
 inline void dev_free(void *p, hipStream_t s) {
     if (!p) return;
@@ -428,8 +440,8 @@ struct Scratch {
     }
     hipError_t alloc(void **p, size_t bytes) {
         bytes = (std::max<size_t>(bytes, 16) + 255) & ~size_t(255);
-        if (borrowed && used + bytes <= t->ws_bytes) { *p = static_cast<char *>(t->ws_p) + used; used += bytes; return hipSuccess; }
-        const hipError_t e = dev_malloc(p, bytes, s);
+        if (borrowed && used + bytes <= t->ws_bytes) { *p = static_cast<char *>(t->ws_p) + used; used += bytes; return debug_fill(*p, bytes, s); }
+        const hipError_t e = dev_malloc(p, bytes, s);   // (which fills what it hands out)
         if (e == hipSuccess) { pool_allocs.push_back(*p); pool_bytes += bytes; }
         return e;
     }

@@ -164,6 +164,8 @@ void daac_iter::run() {
         const uint64_t we = std::min<uint64_t>(len, wb + window_of(k));
         const uint64_t from = wb > halo ? wb - halo : 0;
         const uint64_t skew = from & 15;  // keep the haystack's 16-byte phase for the vector loop
+        // (debug_fill: the whole buffer, in front of every window's copy — it still holds the window before last)
+        if (const hipError_t fe = debug_fill(stage[k & 1], kit->stage_bytes, s_h2d); fe != hipSuccess) return fe;
         if (we > from) {
             const hipError_t e = hipMemcpyAsync(static_cast<uint8_t *>(stage[k & 1]) + skew, hay + from, we - from, hipMemcpyHostToDevice, s_h2d);
             if (e != hipSuccess) return e;
@@ -578,6 +580,7 @@ static daac_status stream_feed_impl(daac_stream *s, const uint8_t *chunk, size_t
         HIP_TRY(hipMalloc(&s->buf[nx], want));
         s->cap[nx] = want;
     }
+    HIP_TRY(debug_fill(s->buf[nx], s->cap[nx], s->stream));   // (new, or as the feed before last left it)
     uint8_t *nb = static_cast<uint8_t *>(s->buf[nx]) + skew;
     if (s->consumed > keep) {
         const uint8_t *old = static_cast<const uint8_t *>(s->buf[s->cur]) + (s->kept_from & 15) + (keep - s->kept_from);

@@ -47,6 +47,10 @@ static bool option_value_ok(const char *name, int id, int64_t value) {
         set_error(std::string("option ") + name + " is a depth of the trie (0 = ROOT's row alone), or -1 to have it chosen");
         return false;
     }
+    if (id == OPT_debug_fill && (value < -1 || value > 255)) {
+        set_error(std::string("option ") + name + " is the byte scratch and result buffers are filled with when they are handed out: 0 .. 255, or -1 for none");
+        return false;
+    }
     return true;
 }
 
@@ -61,7 +65,7 @@ daac_status daac_set_option(const char *name, int64_t value) {
 }
 
 // The same option for ONE handle: overrides the process-wide value for every scan, iterator and stream of `pma`.  `unset` != 0 takes the
-// override away.  `pool` / `pool_keep` (the device's allocator) have no per-handle meaning: status 1.  An option that is read when the
+// override away.  `pool` / `pool_keep` / `debug_fill` (the device's allocator) have no per-handle meaning: status 1.  An option that is read when the
 // tables are laid out (gram_lds_budget, lds_budget, pfx, left3, char_map_lds, char_row_lds, dense_depth, rows_share_pct, gram_rank_in_lds, gram4_mph)
 // can only be set BEFORE the handle's first upload: afterwards the tables keep their layout, so the call changes nothing and says so
 // (DAAC_ERR_UNSUPPORTED) instead of returning OK for an override that would never take effect (round-5 advisor).
@@ -71,7 +75,10 @@ daac_status daac_pma_set_option(daac_pma *pma, const char *name, int64_t value, 
     bool upload = false;
     if (!option_slot(name, value, id, upload)) { set_error(std::string("unknown option: ") + name); return DAAC_ERR_INVALID_ARGUMENT; }
     if (!unset && !option_value_ok(name, id, value)) return DAAC_ERR_INVALID_ARGUMENT;
-    if (id == OPT_pool || id == OPT_pool_keep) { set_error("pool / pool_keep are properties of the device's allocator, not of a handle"); return DAAC_ERR_INVALID_ARGUMENT; }
+    if (id == OPT_pool || id == OPT_pool_keep || id == OPT_debug_fill) {
+        set_error("pool / pool_keep / debug_fill are properties of the device's allocator, not of a handle");
+        return DAAC_ERR_INVALID_ARGUMENT;
+    }
     if (upload) {
         std::lock_guard<std::mutex> g(pma->mu);
         if (!pma->dev.empty()) {

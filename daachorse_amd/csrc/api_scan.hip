@@ -377,6 +377,7 @@ daac_status stage_window(const uint8_t *host_hay, uint64_t copy_from, uint64_t e
     const uint64_t n = end - copy_from;
     const uint64_t skew = copy_from & 15;  // keep the haystack's 16-byte phase for the vector loop
     HIP_TRY(hipMalloc(dbuf, n + skew + 32));
+    HIP_TRY(debug_fill(*dbuf, n + skew + 32, stream));
     if (n) HIP_TRY(hipMemcpyAsync(static_cast<uint8_t *>(*dbuf) + skew, host_hay + copy_from, n, hipMemcpyHostToDevice, stream));
     *virt_base = static_cast<const uint8_t *>(*dbuf) + skew - copy_from;
     return DAAC_OK;
@@ -547,6 +548,7 @@ static daac_status scan_count_impl(daac_pma *pma, int mode, int engine, const ui
     void *flagbuf = nullptr;
     if (pl.leftmost && pma->root_has_output()) {  // the one scan that can hit the non-terminating corner
         HIP_TRY(hipMalloc(&flagbuf, sizeof(unsigned long long)));
+        HIP_TRY(debug_fill(flagbuf, sizeof(unsigned long long), stream));
         HIP_TRY(hipMemsetAsync(flagbuf, 0, sizeof(unsigned long long), stream));
         pl.a.flags = static_cast<unsigned long long *>(flagbuf);
     }
@@ -841,6 +843,8 @@ daac_status daac_scan_count_multi(daac_pma *pma, int mode, int engine, const daa
         w->post([&, mine](ShardWorker &me) {
             const size_t m = mine->size();
             bool ok = !me.failed && me.stream != nullptr && me.reserve(m);
+            // (debug_fill: the job's part of the block, new or as the job before left it)
+            if (ok && debug_fill(me.d_res, m * 3 * sizeof(unsigned long long), me.stream) != hipSuccess) { (void)hipGetLastError(); ok = false; }
             if (!ok) {
                 for (size_t k : *mine) { outs[k].st = DAAC_ERR_DEVICE; outs[k].err = "the shard's device could not be made current (hipSetDevice / stream / result buffers)"; }
             } else {

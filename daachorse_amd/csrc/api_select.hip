@@ -81,7 +81,9 @@ daac_status emit_overlapping3(daac_pma *pma, DeviceTables *t, const uint8_t *dev
     dbg_mark("emit: scratch");
     unsigned long long total = 0, deep_total = 0;
     uint32_t ctl[2] = {0, 0};
+    int attempts = 0;
     for (int attempt = 0;; ++attempt) {
+        attempts = attempt + 1;
         if (chunk_cap >= (1ull << 32) / kEmit3Chunk) return DAAC_OK;
         sc.rewind(sc_mark);
         HIP_TRY(sc.alloc(&g_recs_p, chunk_cap * (static_cast<size_t>(kEmit3Chunk) * sizeof(uint4) + 4)));
@@ -126,7 +128,9 @@ daac_status emit_overlapping3(daac_pma *pma, DeviceTables *t, const uint8_t *dev
     t->emit3_rec_per_kib.store(static_cast<uint32_t>(std::min<uint64_t>(1u << 20, deep_total * 5 / 4 / ((end - begin) / 1024 + 1) + 1)));
     g_last_engine = raw ? DAAC_ENGINE_PFX : DAAC_ENGINE_GRAM;
     const size_t tuple_bytes = out.f16 ? 16 : sizeof(daac_match);
-    if (total == 0) { *served = true; return DAAC_OK; }
+    // daac_last_kernel(): which form served the list and whether the record list had to be sized again (attempts=2: the rerun)
+    const std::string served_line = std::string("emit3 raw=") + (raw ? "1" : "0") + " attempts=" + std::to_string(attempts);
+    if (total == 0) { g_last_kernel = served_line; *served = true; return DAAC_OK; }
     if (!dest && total * tuple_bytes > static_cast<unsigned long long>(OPT(max_result_bytes))) {
         set_error("match list of " + std::to_string(total) + " tuples exceeds max_result_bytes; iterate with daac_iter_* instead");
         return DAAC_ERR_AUTOMATON_SCALE;
@@ -188,6 +192,7 @@ daac_status emit_overlapping3(daac_pma *pma, DeviceTables *t, const uint8_t *dev
     }
     out.f16_done = out.f16;
     t->emit3_gave_up.store(0);
+    g_last_kernel = served_line;
     *served = true;
     dbg_mark("emit: EXPAND read");
     return DAAC_OK;

@@ -100,6 +100,7 @@ daac_status daac_tokenize(daac_pma *pma, int mode, int engine, const uint8_t *ha
     std::unique_ptr<void, void (*)(void *)> g1(staged, [](void *p) { if (p) (void)hipFree(p); });
     TupleList tl(stream);
     uint64_t k = 0;
+    g_last_kernel.clear();   // (the single-haystack tuple call names no kernel: without this the line below kept every earlier call's line behind it)
     if ((st = daac_scan_device16(pma, mode, engine, len ? text : nullptr, len, 1, stream_, reinterpret_cast<daac_match16 **>(&tl.list), &k)) != DAAC_OK) return st;
     return tokens(text, len, tl, k, nullptr, 0, gap, gap_id, stream, o);
 }

@@ -208,7 +208,8 @@ int daac_last_engine(void);
  * The count + checksum GRAM kernels name the compiled instance that ran and the launch's regions: "gram K=3 short=1 waves=16 dense=0 rank=lds ppl=16
  * region=2048 regions=7 slab=1216" (rank: the rank directory in the LDS or read from the L2), "gram2 K=3 dir=1 dense=0 waves=16 region=.. regions=.."
  * (dir=2: 32-bit directory entries), "gram2w exact=1 region=.. regions=.." (exact=0: `.count()` alone); a call that launches nothing
- * (an empty range) says the family alone.
+ * (an empty range) says the family alone.  A materialising overlapping scan that the tuple emitter served says "emit3 raw=0 attempts=1"
+ * (raw=1: the PFX form over the raw text; attempts=2: the record list proved too short and the detection was rerun with the exact size).
  * ABI 6; a diagnostic: the text is not a contract. */
 const char *daac_last_kernel(void);
 
@@ -1110,14 +1111,19 @@ void daac_stream_close(daac_stream *s);
  *   hist_lds_bins (16384)       histograms: the first slots (the shortest patterns: slots are in BFS order of the trie) a workgroup counts in LDS
  *                               before it flushes them to the global counters; clamped to what 160 KB minus the engine's tables hold; 0 = all
  *                               hits go to global atomics (13 to 27 times slower on the cfg3 dictionary); negative: status 1.  The default is the
- *                               winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json) */
+ *                               winner of tools/time_hist.py's sweep on TIERED and DARRAY (profiles/r11_hist_time.json)
+ *   debug_fill (-1)             tests: 0 .. 255 = every scratch, staging and result buffer the library allocates (the pool's blocks, a handle's
+ *                               kept workspace, the staging copies of host text, the iterators' and steppers' buffers) is set to that byte
+ *                               when it is handed out, on the call's stream, in front of the call's own clears and copies; -1 = off (the
+ *                               contents are undefined, as always); any other value: status 1.  Results never depend on it (DESIGN.md 4.24;
+ *                               tests/test_gpu_uninitialised.py).  Not read at upload; process-wide only */
 daac_status daac_set_option(const char *name, int64_t value);
 /* The same option for ONE handle (ABI 5): overrides the process-wide value for every scan, iterator and stream of `pma`, whichever thread runs
  * them (the worker threads of the lazy iterator and of daac_scan_count_multi included).  Two threads scanning two handles with different
  * settings do not share state.  unset != 0 removes the override.  The options read when the tables are laid out (lds_budget, dense_depth,
  * rows_share_pct, gram_lds_budget, gram_rank_in_lds, pfx, char_map_lds, char_row_lds) are set BEFORE the handle's first upload: on a handle
  * that already has tables on a device they could not take effect, and the call says so (status 6, ABI 6) instead of answering OK.
- * `pool` / `pool_keep` belong to the device's allocator, not to a handle (status 1). */
+ * `pool` / `pool_keep` / `debug_fill` belong to the device's allocator, not to a handle (status 1). */
 daac_status daac_pma_set_option(daac_pma *pma, const char *name, int64_t value, int unset);
 
 #ifdef __cplusplus
